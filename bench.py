@@ -20,7 +20,12 @@ per GPU; the key image is built once on rank 0 and broadcast over RCCL/xGMI (tor
 backend "nccl" = RCCL), then every rank bootstraps its own shard with no data-path collective.
 WORLD_SIZE must equal --gpus (exit status 2 otherwise).
 
-Extra JSON fields:
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds per timed step, and the run's shape).  --dump-outputs DIR
+also writes the outputs of the last timed step (seeded inputs: the same arguments give the same inputs on
+every run).  Everything else below -- the other legs and every output check -- runs only with --full.
+
+Extra JSON fields (--full):
   dist          backend and world size torch.distributed reports, per-rank blind-rotation kernel
                 times (max / min), the key broadcast time.
   roofline      the blind-rotation kernel (the dominant one), timed alone with HIP events on its
@@ -117,7 +122,21 @@ def parse():
                     help="launch knob (tfhe_knobs) for A/B runs; repeatable")
     ap.add_argument("--test-lib", action="store_true",
                     help="run on lib/libtfhe_hip_test.so (fault-probe / timing builds; A/B runs only)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg of the line: the blind rotation timed alone "
+                         "(roofline, valu), the host-array entry point, the drop-in, the CPU baseline and the output "
+                         "checks (oracle_sample, parity_ok; a failed check exits 1).  Without it the run only sets "
+                         "up, warms up, times the steps and prints the headline; the options that shape those legs "
+                         "(--kernel-reps, --no-cpu-baseline, --no-host-array, --no-dropin, --cpu-seconds, --pmc-json, "
+                         "--valu-peak-json) then have no effect")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the output ciphertexts of the last step to DIR/out.npy "
+                         "(DIR/out_rank<r>.npy with several ranks) as float64, exact for these words; the inputs are "
+                         "seeded, so two builds run with the same arguments can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def newest(*paths):
@@ -422,6 +441,27 @@ def cpu_baseline_port(p, bsk, ksk, seconds, gpu_sample, reason):
             "gpu_parity": parity}
 
 
+DUMP_BYTES = 60 * MIB   # --dump-outputs: every file of the directory together stays under 64 MB
+
+
+def dump_outputs(outdir, out, world, rank):
+    """--dump-outputs: the timed path's output buffer (B ciphertexts of n + 1 words, what a caller of the
+    device-resident entry point receives) after its last step, as float64 (ciphertext words are below the
+    ciphertext modulus, far under 2^53, so the copy is exact).  A batch too large for the size limit is
+    cut to a fixed seeded sample of its rows, whose indices go to a second file."""
+    os.makedirs(outdir, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    rows = out.shape[0]
+    keep = max(1, DUMP_BYTES // world // (8 * (out.shape[1] + 1)))
+    if rows > keep:
+        idx = np.sort(np.random.default_rng(20240607).choice(rows, size=keep, replace=False))
+        import torch
+
+        out = out[torch.from_numpy(idx).to(out.device)]
+        np.save(os.path.join(outdir, f"out_rows{sfx}.npy"), idx.astype(np.float64))
+    np.save(os.path.join(outdir, f"out{sfx}.npy"), out.cpu().numpy().astype(np.float64))
+
+
 def batch_split(cfg, batch, world, rank):
     """(this rank's batch, the whole job's): weak scaling = `batch` per GPU, strong = `batch` in all, cut into
     contiguous shards (tfhe_shard_range)."""
@@ -559,6 +599,34 @@ def main():
     total_bs = total * bs_per_unit * args.steps
     value = total_bs / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, world, rank)
+
+    info = ctx.info()
+    line = {
+        "metric": metric_name(name, cfg, total, B, world, bool(args.params)),
+        "value": round(value, 2), "unit": "bootstraps/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+        "scaling": cfg["scaling"], "vs_baseline": None, "data": "synthetic",
+        "dtype": {0: "u32" if int(info.word_bits) == 32 else "u64", 1: "u32", 2: "f64",
+                  3: "f64", 4: "i32", 5: "u64"}[int(info.br_kernel)],
+        "config": {"workload": f"{name}: {cfg['what']}, inputs resident in HBM", "config": name,
+                   "global_batch": total, "batch_per_gpu": B, "bootstraps_per_unit": bs_per_unit,
+                   "n": p.n, "N": p.N, "Q": p.Q, "dG2": p.dG2, "parallelism": f"shard{world}"},
+        "full": args.full,
+        "setup_s": round(setup_s, 2), "key_broadcast_ms": None if bcast_ms is None else round(bcast_ms, 2),
+        "key_image_bytes": int(info.key_image_bytes),
+    }
+    if knobs or args.test_lib:
+        line["knobs"] = dict(knobs, test_lib=args.test_lib)
+    if not args.full:
+        # the plain run: the headline alone.  Every other leg and every output check is --full's
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        ctx.GPUClean()
+        if world > 1:
+            dist.destroy_process_group()
+        return 0
 
     # ---- dominant kernel (blind rotation) timed alone with HIP events on its stream ----
     a = torch.randint(0, int(p.q), (B, p.n), dtype=torch.int64, device=dev, generator=g)
@@ -730,16 +798,7 @@ def main():
         print(f"[bench] ERROR: output checks failed: {', '.join(failed)}", file=sys.stderr)
 
     if rank == 0:
-        line = {
-            "metric": metric_name(name, cfg, total, B, world, bool(args.params)),
-            "value": round(value, 2), "unit": "bootstraps/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": cfg["scaling"], "vs_baseline": None, "data": "synthetic",
-            "dtype": {0: "u32" if int(info.word_bits) == 32 else "u64", 1: "u32", 2: "f64",
-                      3: "f64", 4: "i32", 5: "u64"}[int(info.br_kernel)],
-            "config": {"workload": f"{name}: {cfg['what']}, inputs resident in HBM", "config": name,
-                       "global_batch": total, "batch_per_gpu": B, "bootstraps_per_unit": bs_per_unit,
-                       "n": p.n, "N": p.N, "Q": p.Q, "dG2": p.dG2, "parallelism": f"shard{world}"},
+        line.update({
             "value_end_to_end": None if host_array is None else host_array["value"],
             "dist": {"backend": dist.get_backend() if world > 1 else None,
                      "world_size": dist.get_world_size() if world > 1 else 1,
@@ -747,11 +806,7 @@ def main():
                      "key_broadcast_ms": None if bcast_ms is None else round(bcast_ms, 2)},
             "parity_ok": parity_ok, "parity_failed": failed, "oracle_sample": oracle,
             "roofline": roofline, "valu": valu, "host_array": host_array, "dropin": dropin, "cpu_baseline": cpu,
-            "setup_s": round(setup_s, 2), "key_broadcast_ms": None if bcast_ms is None else round(bcast_ms, 2),
-            "key_image_bytes": int(info.key_image_bytes),
-        }
-        if knobs or args.test_lib:
-            line["knobs"] = dict(knobs, test_lib=args.test_lib)
+        })
         print(json.dumps(line), flush=True)
     ctx.GPUClean()
     if world > 1:

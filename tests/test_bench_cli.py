@@ -35,7 +35,7 @@ def test_world_size_without_matching_gpus_exits_2():
 def test_help_lists_configurations():
     r = _run(["--help"])
     assert r.returncode == 0
-    for opt in ("--config", "--batch", "--scaling", "--knob", "--pmc-json", "--test-lib"):
+    for opt in ("--config", "--batch", "--scaling", "--knob", "--pmc-json", "--test-lib", "--full", "--dump-outputs"):
         assert opt in r.stdout
 
 
@@ -97,8 +97,8 @@ def test_oracle_sample_check_catches_one_wrong_word(oracle):
 
 @pytest.mark.gpu
 def test_bench_line_passes_its_own_checks():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "64", "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-dropin"], capture_output=True, text=True, timeout=300,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", "64", "--steps", "1",
+                        "--warmup", "1", "--no-cpu-baseline", "--no-dropin"], capture_output=True, text=True, timeout=300,
                        env={k: v for k, v in os.environ.items() if k != "WORLD_SIZE"})
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -106,8 +106,29 @@ def test_bench_line_passes_its_own_checks():
 
 
 @pytest.mark.gpu
+def test_plain_run_prints_the_headline_alone_and_dumps_its_outputs(tmp_path, oracle):
+    """Without --full: the headline fields and the run's shape, none of the other legs; --dump-outputs writes
+    the last timed step's output ciphertexts (float64 copies of words below q)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "64", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=300,
+                       env={k: v for k, v in os.environ.items() if k != "WORLD_SIZE"})
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["full"] is False and line["steps"] == 2 and line["unit"] == "bootstraps/s"
+    assert line["higher_is_better"] is True and line["dtype"] in ("u32", "i32", "f64", "u64")
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 - 64) <= 0.64
+    for leg in ("roofline", "valu", "host_array", "dropin", "cpu_baseline", "oracle_sample", "parity_ok"):
+        assert leg not in line
+    p = oracle.params_from_set("STD128")
+    a = np.load(tmp_path / "dump" / "out.npy")
+    assert os.listdir(tmp_path / "dump") == ["out.npy"]
+    assert a.dtype == np.float64 and a.shape == (64, p.n + 1)
+    assert np.array_equal(a, np.floor(a)) and a.min() >= 0 and a.max() < p.q and len(np.unique(a)) > p.q // 2
+
+
+@pytest.mark.gpu
 def test_bench_strong_scaling_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "96", "--scaling", "strong",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", "96", "--scaling", "strong",
                         "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-dropin", "--no-host-array"],
                        capture_output=True, text=True, timeout=300,
                        env={k: v for k, v in os.environ.items() if k != "WORLD_SIZE"})
@@ -123,8 +144,8 @@ def test_bench_exits_nonzero_on_wrong_outputs():
     word acc1[0]; duo = 0 keeps this small batch on f64w) makes the benchmarked outputs wrong: the line
     says so and the process fails.  (Probe 3, the prologue race, cannot do it here: the gate pipeline's
     test-vector accumulators have acc0 = 0, and the race only overwrites zeros with zeros.)"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C5a", "--batch", "8", "--steps",
-                        "1", "--warmup", "1", "--no-cpu-baseline", "--test-lib", "--knob", "probe=6", "--knob", "duo=0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "C5a", "--batch", "8",
+                        "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--test-lib", "--knob", "probe=6", "--knob", "duo=0"],
                        capture_output=True, text=True, timeout=300,
                        env={k: v for k, v in os.environ.items() if k != "WORLD_SIZE"})
     assert r.returncode == 1, r.stderr[-3000:]

@@ -9,7 +9,7 @@ O=gpurun_out/$TAG
 mkdir -p $O
 for CFG in $CFGS; do
   echo "[$(date +%T)] $CFG"
-  timeout -k 10 600 python3 bench.py --config $CFG > $O/bench_$CFG.log 2>&1 || { echo "bench_all rc=$?"; exit 1; }
+  timeout -k 10 600 python3 bench.py --full --config $CFG > $O/bench_$CFG.log 2>&1 || { echo "bench_all rc=$?"; exit 1; }
   tail -1 $O/bench_$CFG.log | cut -c1-200
 done
 echo "bench_all rc=0"

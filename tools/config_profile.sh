@@ -10,7 +10,7 @@
 set -u
 TAG=$1
 CFGS=$2
-EXTRA=${3:-}
+EXTRA="--full ${3:-}"  # every bench.py run below reads legs that only --full runs
 export TMPDIR=/tmp
 O=gpurun_out/$TAG
 mkdir -p $O

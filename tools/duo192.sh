@@ -8,7 +8,7 @@ mkdir -p $O
 for B in 64 128; do
   for r in 1 2; do
     for k in 128 0; do
-      timeout -k 10 200 python3 bench.py --params STD192 --batch $B --steps 5 --warmup 1 --no-host-array --knob duo=$k \
+      timeout -k 10 200 python3 bench.py --full --params STD192 --batch $B --steps 5 --warmup 1 --no-host-array --knob duo=$k \
         > $O/std192_B${B}_duo${k}_$r.log 2>&1 || { echo "rc=$?"; exit 1; }
       tail -1 $O/std192_B${B}_duo${k}_$r.log | python3 -c "
 import json, sys

@@ -9,7 +9,7 @@ TAG=$1; CFG=$2; LIBS=$3; R=${4:-2}
 export TMPDIR=/tmp
 O=gpurun_out/$TAG
 mkdir -p $O
-Q="--config $CFG --no-cpu-baseline --no-host-array --no-dropin --steps 1 --warmup 1 --kernel-reps 1"
+Q="--full --config $CFG --no-cpu-baseline --no-host-array --no-dropin --steps 1 --warmup 1 --kernel-reps 1"
 for r in $(seq 1 $R); do
   i=0
   for L in $LIBS; do
@@ -17,7 +17,7 @@ for r in $(seq 1 $R); do
     echo "[$(date +%T)] lib$i rep $r ($L)"
     TFHE_ABI_PREV=1 TFHE_LIB=$L timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE -d $O/f_${i}_$r -o run --output-format csv -- python3 bench.py $Q > $O/f_${i}_$r.log 2>&1 || { echo "rc=$?"; exit 1; }
     TFHE_ABI_PREV=1 TFHE_LIB=$L timeout -s KILL 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum -d $O/h_${i}_$r -o run --output-format csv -- python3 bench.py $Q > $O/h_${i}_$r.log 2>&1 || { echo "rc=$?"; exit 1; }
-    TFHE_ABI_PREV=1 TFHE_LIB=$L timeout -k 10 300 python3 bench.py --config $CFG --no-cpu-baseline --no-host-array --no-dropin --steps 2 --warmup 1 > $O/b_${i}_$r.log 2>&1 || { echo "rc=$?"; exit 1; }
+    TFHE_ABI_PREV=1 TFHE_LIB=$L timeout -k 10 300 python3 bench.py --full --config $CFG --no-cpu-baseline --no-host-array --no-dropin --steps 2 --warmup 1 > $O/b_${i}_$r.log 2>&1 || { echo "rc=$?"; exit 1; }
   done
 done
 python3 - $O "$LIBS" $R <<'PY'

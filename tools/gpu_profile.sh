@@ -7,7 +7,7 @@
 # Each GPU step has its own time limit; the chain stops at the first failure.
 set -u
 TAG=${1:-r01}
-ARGS=${2:-}
+ARGS="--full ${2:-}"  # every bench.py run below reads legs that only --full runs
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 timeout -k 10 400 python3 bench.py $ARGS > gpurun_out/bench_$TAG.log 2>&1 &&

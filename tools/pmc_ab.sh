@@ -8,7 +8,7 @@ TAG=$1; CFG=$2; LIBS=$3
 export TMPDIR=/tmp
 O=gpurun_out/$TAG
 mkdir -p $O
-Q="--config $CFG --no-cpu-baseline --no-host-array --no-dropin --steps 1 --warmup 1 --kernel-reps 1"
+Q="--full --config $CFG --no-cpu-baseline --no-host-array --no-dropin --steps 1 --warmup 1 --kernel-reps 1"
 i=0
 for L in $LIBS; do
   i=$((i + 1))

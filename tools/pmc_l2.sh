@@ -12,7 +12,7 @@ O=gpurun_out/$TAG
 mkdir -p $O
 for CFG in $CFGS; do
   timeout -s KILL 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_DRAM_sum \
-    -d $O/pmcl2_$CFG -o run --output-format csv -- python3 bench.py --config $CFG --no-cpu-baseline --no-host-array \
+    -d $O/pmcl2_$CFG -o run --output-format csv -- python3 bench.py --full --config $CFG --no-cpu-baseline --no-host-array \
     --no-dropin --steps 1 --warmup 1 --kernel-reps 1 > $O/pmcl2_$CFG.log 2>&1 || exit $?
   python3 - $O/pmcl2_$CFG $CFG <<'PY' > $O/pmcl2_$CFG.json || exit $?
 import collections, csv, glob, json, sys

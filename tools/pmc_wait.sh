@@ -7,7 +7,7 @@ set -u
 TAG=${1:-wait}
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-B=${CMD:-"python3 bench.py --no-cpu-baseline --steps 1 --warmup 0"}
+B=${CMD:-"python3 bench.py --full --no-cpu-baseline --steps 1 --warmup 0"}
 timeout -s KILL 200 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU SQ_ACTIVE_INST_VALU -d gpurun_out/${TAG} -o run --output-format csv -- $B > gpurun_out/${TAG}.log 2>&1
 rc=$?
 python3 - "$TAG" <<'PY'
