@@ -130,7 +130,7 @@ typedef struct tfhe_info {
 #define TFHE_BR_F64 2          /* exact-FP64 kernel, blind_rotate_f64.hip */
 #define TFHE_BR_F64_FOLD 3     /* exact-FP64 kernel, top digit's transforms eliminated */
 #define TFHE_BR_RNS 4          /* (retired in round 3: the four-prime RNS kernel; never returned) */
-#define TFHE_BR_SF 5           /* special-form u64 kernel (Q = 2^54 - c), blind_rotate_generic.hip sf2 / gen3sf */
+#define TFHE_BR_SF 5           /* special-form u64 kernel (Q = 2^54 - c), blind_rotate_sf.hip sf2 / gen3sf */
 
 typedef struct tfhe_ctx tfhe_ctx;
 

@@ -1,4 +1,4 @@
-"""GPU: the two-workgroup two-digit special-form blind rotation (k_blind_rotate_sfduo<2>, blind_rotate_generic.hip;
+"""GPU: the two-workgroup two-digit special-form blind rotation (k_blind_rotate_sfduo<2>, blind_rotate_sf.hip;
 round 6: split by NTT half -- the round-4/5 form split by accumulator polynomial, k_blind_rotate_sf2duo, is the test
 library's A/B form and is checked against it below).
 

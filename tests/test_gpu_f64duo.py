@@ -132,7 +132,7 @@ def test_f64duo_partner_timeout_is_recomputed(oracle):
 def test_f64duo_two_streams_and_two_contexts(oracle):
     """Verdict r5 item 7: the duo form outside its usual single-stream use.
     * One context, two streams, no host sync between the launches: the device's one exchange buffer is
-      fenced (kernels.hpp duo_serialised), so both batches are exact and no partner times out.
+      fenced (duo.hpp duo_serialised), so both batches are exact and no partner times out.
     * Two contexts (two exchange buffers), 128 + 128 ciphertexts launched at once on two streams: 512
       workgroups that need one CU each, so some members may run while their partners wait behind the other
       launch.  The partner wait is bounded by time (10 ms of s_memrealtime per round), a timed-out pair is

@@ -1,5 +1,5 @@
 """GPU: the one-digit special-form blind rotation on two workgroups per ciphertext (k_blind_rotate_sfduo<1>,
-blind_rotate_generic.hip; verdict r5 "missing" 2).
+blind_rotate_sf.hip; verdict r5 "missing" 2).
 
 C3's context class (arbFunc logQ 12: Q = 2^54 - 77823, N = 2048, one transformed digit after one thrown)
 runs batches of at most tfhe_knobs.duo (default 128) ciphertexts -- and at most the device's co-resident

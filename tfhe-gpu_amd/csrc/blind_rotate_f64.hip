@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "device_math.hpp"
+#include "duo.hpp"
 #include "kernels.hpp"
 
 namespace tfhe {
@@ -161,7 +162,7 @@ __device__ __forceinline__ uint32_t f64_tau() {
     return tau;
 }
 
-// ---- N = 2048, wave-local passes (f64w; the sf2 design of blind_rotate_generic.hip) ----------
+// ---- N = 2048, wave-local passes (f64w; the sf2 design of blind_rotate_sf.hip) ----------
 // Wave w owns the 256-element block w of both polynomials after pass A: passes B, C and the
 // units run in wave w without workgroup barriers, the units leave slots 4u .. 4u+3 (u = 64w + l)
 // of both polynomials in registers, and the products (32-byte key rows per lane), the C' update,
@@ -285,7 +286,7 @@ __device__ __forceinline__ void f64w_ntt_inv(double* buf, const double (&s)[2][4
 // barrier before each further digit's pass A; 6 (fault injection, tests/test_bench_cli.py) flips bit 40 of
 // ciphertext 0's acc1[0] (the extracted b: large enough to survive every modulus switch after it)
 // RESCUE (launched behind every f64wduo launch): only the ciphertexts whose duo pair timed out (the pair's
-// failed word, kernels.hpp DuoBuf) run, from their saved inputs; the others exit at once
+// failed word, duo.hpp DuoBuf) run, from their saved inputs; the others exit at once
 #ifndef F64W_KPRE
 #define F64W_KPRE 0
 #endif
@@ -694,25 +695,12 @@ __device__ __forceinline__ void f64d_inv(double* bi, const double (&s)[4], doubl
     }
 }
 
-__device__ __forceinline__ void duo_store_d(double* p, double v) {
-    __hip_atomic_store(reinterpret_cast<uint64_t*>(p), __builtin_bit_cast(uint64_t, v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double duo_load_d(const double* p) {
-    return __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<uint64_t*>(const_cast<double*>(p)),
-                                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-#ifndef F64D_MFULL
-#define F64D_MFULL 1
-#endif
-#ifndef F64D_FSW
-#define F64D_FSW 1
-#endif
-// row e of the whole factor table lives at e ^ (bits 5-9 of e): a wave's exponents (2 bitrev(slot) + 1) a'
+// The whole 2N-entry factor table psi^e - 1 in LDS (32 KiB; one workgroup per CU leaves the room), one lookup
+// per factor.  Row e lives at e ^ (bits 5-9 of e): a wave's exponents (2 bitrev(slot) + 1) a'
 // share their low five bits, so unswizzled every lane of a 32-lane group hit one bank pair (a 32-way
 // conflict on each of the 8 lookups per lane-round; mean 29.4 distinct addresses per bank over random a');
 // with the fold the mean is 2.0 (bit 5 up varies as m a' for the group's 32 values of m)
-__device__ __forceinline__ uint32_t fsw(uint32_t e) { return F64D_FSW ? e ^ ((e >> 5) & 31) : e; }
+__device__ __forceinline__ uint32_t fsw(uint32_t e) { return e ^ ((e >> 5) & 31); }
 #ifndef F64D_KPRE
 #define F64D_KPRE 4
 #endif
@@ -724,18 +712,7 @@ __device__ __forceinline__ uint32_t fsw(uint32_t e) { return F64D_FSW ? e ^ ((e 
 // partner that never arrives would, and the wait is a 64th of the 10 ms bound.  PROBE 2 (timing only, results
 // invalid): no hand-off at all -- each member takes its own stage-1 values for its partner's -- the
 // bound on what the exchange costs per round
-// Hardware assumptions of the hand-off (verdict r5 item 7):
-//  * ordering: the data stores and the flag are RELAXED agent-scope atomics (write-through past the CU, `sc1`);
-//    the data is ordered before the flag by every wave's `s_waitcnt vmcnt(0)` (each store acknowledged) and the
-//    workgroup barrier, and on the reader by the poll's load returning before the barrier and the loads behind
-//    it.  That is gfx9 ISA behaviour (the MI355X_MICROARCH.md hand-off table's sc1 row), not a HIP-memory-model
-//    release / acquire pair -- one of those costs about 1.7 us per round, more than the hand-off itself;
-//  * pairing: members b and b + 8 share an XCD only through round-robin workgroup dispatch; correctness never
-//    depends on it (agent scope), the latency does (same-XCD hand-offs measured 1.1-1.3 us, cross-XCD 1.9-2.0);
-//  * liveness: both members must be resident at once.  The launcher runs the duo form only for batches up to the
-//    device's co-resident pairs (one 116-KiB workgroup per CU: half the CU count) and fences duo launches of one
-//    device's buffer across streams; a partner still missing after 10 ms of wall clock (s_memrealtime, e.g.
-//    behind another context's kernel) fails the pair, and the rescue launch recomputes it exactly.
+// The hand-off, its hardware assumptions and the bounded wait: duo.hpp.
 // The hand-off is one flag per member per round (workgroup barrier, t == 0 stores / polls, barrier).  Forms
 // measured against it and removed (tools/duo_probe.py, us per round at 128 ciphertexts): data-tagged granules
 // (value + round tag in one 8-byte word, no flag or barriers) polling the four words one after another 8.03
@@ -758,10 +735,8 @@ k_blind_rotate_f64wduo(BRParams P, F64Const K, const double* __restrict__ tabs, 
     double* bi = bf + 2 * H;     // inverse buffer [2][H]
     double* cx = bi + 2 * H;     // this round's C' (+ the WRAP correction) [2][H], slot positions
     double* dx = cx + 2 * H;     // LD = 2: digit 0's values for the other column's waves [2][H] (digit 1: bf)
-    // F64D_MFULL: the whole 2N-entry factor table psi^e - 1 (32 KiB; one workgroup per CU leaves the LDS for
-    // it), one lookup per factor; otherwise the two 64-entry tables, two lookups and a product per factor
-    double* mt = dx + (LD > 1 ? 2 * H : 0);  // monomial tables
-    uint32_t* ex = reinterpret_cast<uint32_t*>(mt + (F64D_MFULL ? 2 * N : 128));  // rotation exponents [n]
+    double* mt = dx + (LD > 1 ? 2 * H : 0);  // the whole factor table [2N] (fsw)
+    uint32_t* ex = reinterpret_cast<uint32_t*>(mt + 2 * N);  // rotation exponents [n]
     __shared__ int wflag[2];
     __shared__ uint32_t duo_ok;
     const uint32_t t = threadIdx.x, l = t & 63, w = t >> 6, twoN = 2 * N, logG = P.logG;
@@ -772,15 +747,7 @@ k_blind_rotate_f64wduo(BRParams P, F64Const K, const double* __restrict__ tabs, 
     const uint32_t sp = j * H + 256 * (w & 3);                // their buffer block
     for (uint32_t k = t; k < twoN; k += TH) lds_d[k] = tabs[k];
     const double* mono = tabs + twoN;
-    if constexpr (F64D_MFULL) {
-        for (uint32_t k = t; k < twoN; k += TH) mt[fsw(k)] = mono[k];  // centred psi^k - 1 (k_pack_f64)
-    } else {
-        for (uint32_t k = t; k < 128; k += TH) {
-            const uint32_t e = k < 64 ? 64 * k : k - 64;
-            const double v = __dadd_rn(mono[e], 1.0);
-            mt[k] = v > 0.5 * K.Q ? __dsub_rn(v, K.Q) : v;
-        }
-    }
+    for (uint32_t k = t; k < twoN; k += TH) mt[fsw(k)] = mono[k];  // centred psi^k - 1 (k_pack_f64)
     const double* bsk = tabs + 2 * twoN;
     const uint64_t Qhalf = P.Q >> 1;
     const int64_t Qs = (int64_t)P.Q, Bh = (int64_t)1 << (logG - 1);
@@ -923,8 +890,7 @@ k_blind_rotate_f64wduo(BRParams P, F64Const K, const double* __restrict__ tabs, 
             uint32_t ip = ((2 * (__builtin_bitreverse32(uo + s) >> 21) + 1) * ai) & (twoN - 1);
             if constexpr (PROBE == 3) ip = ai & (twoN - 1);  // timing only: wave-uniform table rows
             const uint32_t in = (twoN - ip) & (twoN - 1);
-            const double Wp = F64D_MFULL ? mt[fsw(ip)] : __dsub_rn(fmodmul(mt[ip >> 6], mt[64 + (ip & 63)], K), 1.0);
-            const double Wm = F64D_MFULL ? mt[fsw(in)] : __dsub_rn(fmodmul(mt[in >> 6], mt[64 + (in & 63)], K), 1.0);
+            const double Wp = mt[fsw(ip)], Wm = mt[fsw(in)];
             S[s] = fred(__dadd_rn(fmodmul(A[0][s], Wp, K), fmodmul(A[1][s], Wm, K)), K);
             Cn[s] = fred(__dadd_rn(Cn[s], S[s]), K);
         }
@@ -936,32 +902,15 @@ k_blind_rotate_f64wduo(BRParams P, F64Const K, const double* __restrict__ tabs, 
         double lo[4], hi[4];
         if constexpr (PROBE != 2) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) duo_store_d(mine + 512 * k + t, o[k]);
+            for (int k = 0; k < 4; ++k) duo_store(mine + 512 * k + t, o[k]);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // every wave's stores drained; every read of the inverse buffer done
-        if (PROBE != 2 && t == 0) {
-            // the wait is bounded by time (wall clock, s_memrealtime): kDuoWaitMs, PROBE 1 a 64th of it
+        if (PROBE != 2 && t == 0) {  // the hand-off protocol: duo.hpp
             const bool gone = PROBE == 1 && pair == 0 && h == 1 && i >= 2;
-            if (!gone) __hip_atomic_store(myflag, i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // (the clock is read every 8th poll, the deadline set at the first read: a partner within 8 polls
-            // costs no clock read)
-            bool ok = !gone;
-            uint64_t t_end = 0;
-            uint32_t k = 0;
-            while (ok && __hip_atomic_load(const_cast<uint32_t*>(peerflag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < i + 1) {
-                if ((++k & 7) == 0) {
-                    const uint64_t now = wall_clock64();
-                    if (t_end == 0) t_end = now + (PROBE ? X.wait_ticks >> 6 : X.wait_ticks);
-                    else if (now > t_end) ok = false;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
+            const bool ok = duo_publish_and_wait<PROBE != 0>(myflag, peerflag, i, X.wait_ticks, gone);
             duo_ok = ok;
-            if (!ok) {
-                __hip_atomic_store(X.flags + pair * 2 * 32 + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_fetch_add(X.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            if (!ok) duo_fail_pair(X, pair);
         }
         if constexpr (PROBE != 2) {
             __syncthreads();
@@ -969,7 +918,7 @@ k_blind_rotate_f64wduo(BRParams P, F64Const K, const double* __restrict__ tabs, 
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const double pv = PROBE == 2 ? o[k] : duo_load_d(theirs + 512 * k + t);
+            const double pv = PROBE == 2 ? o[k] : duo_load(theirs + 512 * k + t);
             lo[k] = h ? pv : o[k];
             hi[k] = h ? o[k] : pv;
         }
@@ -1173,7 +1122,7 @@ hipError_t launch_blind_rotate_f64(const BRParams& P, const DevTables& T, const 
         if (duo_shape && duo && B <= (size_t)kn.duo && B <= duo->resident_pairs && B <= kDuoMaxPairs) {
             // two workgroups per ciphertext (f64wduo), then the rescue of timed-out pairs
             const DuoBuf X = duo_layout(*duo);
-            const size_t ldsd = ((size_t)2 * P.N + 3 * P.N + (ld > 1 ? P.N : 0) + (F64D_MFULL ? 2 * P.N : 128)) *
+            const size_t ldsd = ((size_t)2 * P.N + 3 * P.N + (ld > 1 ? P.N : 0) + 2 * P.N) *
                                     sizeof(double) + rot_exponent_bytes(P.n);
             auto dk = red ? k_blind_rotate_f64wduo<0, true, true, 1> : k_blind_rotate_f64wduo<0, false, false, 2>;
             auto rk = red ? k_blind_rotate_f64w<true, true, 1, 0, true> : k_blind_rotate_f64w<false, false, 2, 0, true>;

@@ -67,7 +67,7 @@ __device__ __forceinline__ double fmodmul_f64(double a, double b, double Q, doub
     return __dadd_rn(__fma_rn(-q, Q, h), l);
 }
 
-// Special-form product for Q = 2^54 - c, c < 2^20 (the sf kernels of blind_rotate_generic.hip;
+// Special-form product for Q = 2^54 - c, c < 2^20 (the sf kernels of blind_rotate_sf.hip;
 // also timed alone by tools/microbench/valu_rates.hip).  The constant w is held as (W0, W1) =
 // (w, w 2^32 mod Q), both < Q; for ANY a < 2^64, a0 = a mod 2^32, a1 = a >> 32 (register halves):
 //     S = a0 W0 + a1 W1 < 2^87
@@ -122,7 +122,7 @@ __device__ __forceinline__ void stage_rot_exponents(uint32_t* ex, const uint64_t
 }
 __host__ __device__ constexpr size_t rot_exponent_bytes(uint32_t n) { return ((size_t)n * 4 + 15) & ~(size_t)15; }
 
-// The NTT-half duo kernels (f64wduo, blind_rotate_f64.hip; sfduo, blind_rotate_generic.hip): buffer index of
+// The NTT-half duo kernels (f64wduo, blind_rotate_f64.hip; sfduo, blind_rotate_sf.hip): buffer index of
 // element x of a half polynomial (block x >> 8, y = x & 255).  y's low five bits are XORed with f(y[7:5]):
 // bit 5 -> bits 1, 3; bit 6 -> bit 4; bit 4 -> bits 0, 2, so that every b64 read is conflict-free per 32-lane
 // group (64 banks) AND every b64 write per 16-lane group (32 banks; MI355X_MICROARCH.md "LDS"), for every pass,

@@ -26,6 +26,7 @@
 #include <thread>
 #include <vector>
 
+#include "duo.hpp"
 #include "host_math.hpp"
 #include "kernels.hpp"
 #include "tfhe_hip.h"
@@ -123,7 +124,7 @@ struct Device {
     void* keys_sf = nullptr;   // special-form path: W1 = w 2^32 mod Q of the arena's tables and BSK, factor rows
     void* ks40 = nullptr;      // split-word key-switch records of 8-byte keys (ks_tiled.hip k_pack_ks40)
     DuoDev duo;                // two-workgroup forms (sf2duo, f64wduo): exchange buffers, wait deadline, co-resident
-                               // pairs, launch fence (kernels.hpp DuoDev; alloc_duo)
+                               // pairs, launch fence (duo.hpp DuoDev; alloc_duo)
     Scratch sc;
     DevTables tables{};
     hipStream_t stream2 = nullptr;  // copy stream of the host-array runner

@@ -1,5 +1,5 @@
 """Worst-case magnitude model of the special-form u64 blind rotations (gen3sf, sf2 in
-blind_rotate_generic.hip) for Q = 2^k - c (k = 54; c = 77823, the logQ / arbFunc contexts, and
+blind_rotate_sf.hip) for Q = 2^k - c (k = 54; c = 77823, the logQ / arbFunc contexts, and
 c = 2^20 - 1, the largest c sf_path_supported admits).
 
 Arithmetic (round 4, device_math.hpp sf_mul): every constant w (twiddle, key, monomial) is stored
@@ -134,14 +134,11 @@ def inv_r4(x, fold_stage):
     return v
 
 
-# folds of the kernel (must match blind_rotate_generic.hip gen3sf)
+# folds of the kernel (must match blind_rotate_sf.hip gen3sf)
 FWD_FOLD_PASS = False       # forward: no folds (growth kQ per stage, 11 stages)
 INV_FOLD_UNITS = (False, True)    # inverse radix-4 units: fold the second stage's sums
 INV_FOLD_PASS = (False, False, True)   # inverse radix-8 passes C, B: fold the last stage's sums
 INV_FOLD_LAST = (False, False, False)  # pass A: none (the accumulator update folds)
-
-
-DUO_MFULL = True  # sf2duo's factors from the whole 2N-row table (SF2D_MFULL, blind_rotate_generic.hip)
 
 
 def model(rows, sf2=True, form="sf2"):
@@ -156,7 +153,7 @@ def model(rows, sf2=True, form="sf2"):
     # sf2p, sf2duo: r + Q with the offset in the difference (ct_ofs)
     global CT
     CT = ct_ofs if form in ("sf2p", "duo") else ct
-    mfull = form in ("sf2p", "sfduo") or (form == "duo" and DUO_MFULL)
+    mfull = form in ("sf2p", "duo", "sfduo")  # the whole 2N-row factor table (sf_factor_full, blind_rotate_sf.hip)
     x = (FWD_OFF * Q - Q // 2, FWD_OFF * Q + Q // 2) if sf2 else (FWD_OFF * Q, (FWD_OFF + 1) * Q)
     if form in ("sf2p", "duo"):
         x = (0, 2 * Q)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Checks the wave-local N = 2048 transform schedule of sf2 (blind_rotate_generic.hip) and f64w
+"""Checks the wave-local N = 2048 transform schedule of sf2 (blind_rotate_sf.hip) and f64w
 (blind_rotate_f64.hip).
 
 Thread t of the 512 (wave w = t >> 6, lane l = t & 63):

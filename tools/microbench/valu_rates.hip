@@ -218,7 +218,7 @@ __global__ void k_modmul_f64(double* out, int iters, uint32_t seed) {
 // The products the N = 2048 kernels actually issue, from the kernels' own header (device_math.hpp):
 // fmodmul_f64 (blind_rotate_f64.hip: 6 FP64 instructions) at STD192's Q = 2^37 - 2^17 + 1 and
 // STD128Q's Q = 2^50 - 2^14 + 1 with full-width centred operands, and sf_mul (the sf kernels of
-// blind_rotate_generic.hip: five v_mad_u64_u32 + four more VALU) at Q = 2^54 - 77823 with lazy operands.
+// blind_rotate_sf.hip: five v_mad_u64_u32 + four more VALU) at Q = 2^54 - 77823 with lazy operands.
 // Each lane runs 8 independent chains x = x * w mod Q, w a per-chain constant (a key / twiddle).
 template <uint64_t QV>
 __global__ void k_modmul_fmod(double* out, int iters, uint32_t seed) {
