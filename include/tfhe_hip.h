@@ -218,6 +218,56 @@ tfhe_status tfhe_eval_floor_device(tfhe_ctx* ctx, size_t B, const uint64_t* d_ct
 tfhe_status tfhe_eval_sign_device(tfhe_ctx* ctx, size_t B, const uint64_t* d_ct, uint64_t mod, uint64_t* d_out,
                                   void* stream);
 
+/* ---- levelled Boolean circuits (no reference counterpart; added without an ABI version change: new
+ * symbols only) ----
+ * A netlist of mixed gates is compiled once and evaluated on `instances` independent input sets in one
+ * call: every level runs as ONE batch of width * instances bootstraps, whatever gate types it mixes
+ * (all gates share the blind rotation; they differ in the linear combination of their operands and in
+ * two test-vector constants, which the level's preparation kernel reads per gate).
+ *
+ * Netlist: wires 0 .. num_inputs-1 are the inputs; gate g defines wire num_inputs + g and may read only
+ * lower-numbered wires.  op is a tfhe_gate value or a tfhe_circuit_op; in1 is ignored for NOT, both
+ * operands for the constants.  An output may name any wire.  Anything else (unknown op, forward or
+ * out-of-range wire, no outputs, a null pointer) is TFHE_ERR_INVALID_ARGUMENT, the message naming the gate.
+ *
+ * Lowering (results equal the vector gate API called gate by gate, bit for bit): XOR / XNOR become the three
+ * bootstraps the vector gate runs for them (binfhe-base-scheme.cpp:619-640), NOT becomes a negate flag
+ * on whatever reads it (EvalNOT, binfhe-base-scheme.cpp:147-159), constants become operand kinds
+ * (NoiselessEmbedding, lwe-pke.cpp:326-338); nothing else is simplified, so
+ * bootstraps = #(OR, AND, NOR, NAND, XOR_FAST, XNOR_FAST) + 3 #(XOR, XNOR).  Inputs and constants are
+ * level 0, NOT is transparent, a bootstrapped gate sits at 1 + the larger of its operands' levels.
+ *
+ * A run keeps every bootstrap's result in a per-device wire store of bootstraps * instances * (n+1) words,
+ * owned by the context and grown on demand (slots are not reused by liveness). */
+typedef enum tfhe_circuit_op {        /* 0..7 are tfhe_gate's values */
+    TFHE_C_NOT = 8, TFHE_C_CONST0 = 9, TFHE_C_CONST1 = 10
+} tfhe_circuit_op;
+typedef struct tfhe_circuit_gate { uint32_t op, in0, in1; } tfhe_circuit_gate;
+typedef struct tfhe_circuit_info {
+    uint32_t num_inputs, num_outputs, num_gates;
+    uint32_t bootstraps;     /* per instance, after lowering */
+    uint32_t levels, widest_level;
+} tfhe_circuit_info;
+typedef struct tfhe_circuit tfhe_circuit;
+
+tfhe_status tfhe_circuit_compile(tfhe_circuit** out, uint32_t num_inputs, const tfhe_circuit_gate* gates,
+                                 size_t num_gates, const uint32_t* outputs, size_t num_outputs);
+/* also releases the plan copies on every device that ran the circuit; no call may be using it */
+tfhe_status tfhe_circuit_free(tfhe_circuit* c);
+tfhe_status tfhe_circuit_get_info(const tfhe_circuit* c, tfhe_circuit_info* out);
+/* widths[l] = bootstraps of level l + 1, l < info.levels <= cap */
+tfhe_status tfhe_circuit_level_widths(const tfhe_circuit* c, uint32_t* widths, size_t cap);
+/* the lowered plan on clear bits: in[num_inputs][instances], out[num_outputs][instances] (no GPU) */
+tfhe_status tfhe_circuit_eval_plain(const tfhe_circuit* c, size_t instances, const uint8_t* in, uint8_t* out);
+/* d_in[num_inputs][instances][n+1] mod q -> d_out[num_outputs][instances][n+1]; q must divide 2N.  Runs on
+ * the context's device that holds d_out, on `stream`; a level wider than 65,536 bootstraps runs in slices. */
+tfhe_status tfhe_eval_circuit_device(tfhe_ctx* ctx, const tfhe_circuit* c, size_t instances, const uint64_t* d_in,
+                                     uint64_t q, uint64_t* d_out, void* stream);
+/* the same on host arrays, staged through the context's first device (levels depend on each other, so a
+ * circuit is not sharded over devices) */
+tfhe_status tfhe_eval_circuit(tfhe_ctx* ctx, const tfhe_circuit* c, size_t instances, const uint64_t* in, uint64_t q,
+                              uint64_t* out);
+
 /* ---- key replication for one-process-per-GPU deployments ----
  * The packed device key image (NTT-domain BSK with Shoup companions, packed
  * KSK, tables) can be copied device-to-device (e.g. broadcast over RCCL/xGMI by
@@ -281,7 +331,8 @@ typedef struct tfhe_knobs {
     int32_t f64w;         /* retired: must be 1 (round 5 removed the slot-layout FP64 kernel 0 selected) */
     int32_t sf2;          /* 0: gen3sf special-form blind rotation instead of the wave-local sf2 */
     int32_t generic;      /* generic kernel form: 0 by N; 1 v1 (digits in LDS); 2 v2 also at N = 2048 */
-    int32_t trace;        /* host-array runner timeline on stderr */
+    int32_t trace;        /* host-array runner timeline on stderr; circuit runs: event-timed total and the share of the
+                             preparation and output kernels */
     int32_t probe;        /* test library only (lib/libtfhe_hip_test.so): fault-probe / timing builds */
     int32_t duo;          /* one- and two-digit special-form contexts (sfduo) and STD128Q- / STD192-class FP64 contexts (f64wduo):
                              batches up to this size (default 128, at most 256) run each ciphertext on two

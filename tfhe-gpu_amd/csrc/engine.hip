@@ -26,6 +26,7 @@
 #include <thread>
 #include <vector>
 
+#include "circuit.hpp"
 #include "duo.hpp"
 #include "host_math.hpp"
 #include "kernels.hpp"
@@ -41,6 +42,12 @@ tfhe_status fail(tfhe_status s, const std::string& msg) {
     g_last_error = msg;
     return s;
 }
+
+}  // namespace
+
+tfhe_status tfhe::set_last_error(tfhe_status s, const std::string& msg) { return fail(s, msg); }
+
+namespace {
 
 #define HCHECK(expr)                                                                                   \
     do {                                                                                               \
@@ -143,6 +150,11 @@ struct Device {
     uint32_t* flags = nullptr;
     size_t flags_words = 0;
     BRDone br_done{};
+    // Wire store of the circuit path (dev_circuit): [bootstraps][instances][n+1] words, every bootstrap's
+    // result of one run.  Grow-only, resized only behind sc_fence (ensure_wires), used inside the
+    // run_device_op frame like the scratch.
+    uint64_t* wires = nullptr;
+    size_t wires_words = 0;
 };
 
 // hipMalloc'd buffer owned by one scope (error paths free it too)
@@ -442,6 +454,7 @@ void free_device(Device& d) {
     hipFree(d.keys_f64);
     hipFree(d.keys_sf);
     hipFree(d.ks40);
+    hipFree(d.wires);
     hipFree(d.duo.base);
     if (d.duo.fence) hipEventDestroy(d.duo.fence);
     delete d.duo.mu;
@@ -493,7 +506,8 @@ tfhe_status device_for(tfhe_ctx* c, const void* p, Device*& out) {
         return TFHE_OK;
     }
     hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    // (the runtime reports plain host memory as success + hipMemoryTypeUnregistered)
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type == hipMemoryTypeUnregistered) {
         (void)hipGetLastError();
         return fail(TFHE_ERR_INVALID_ARGUMENT, "not a device buffer");
     }
@@ -752,6 +766,119 @@ tfhe_status dev_sign(tfhe_ctx* c, Device& d, const uint64_t* ct, uint64_t mod, u
     tv.fmod = q;
     SCHECK(dev_bootstrap(c, d, tv, 0, tmp, out, B));
     HCHECK(launch_lwe_op(LWE_SUB_CONST, n, q, q >> 2, out, nullptr, out, B, s));
+    return TFHE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// circuits (tfhe_circuit, circuit.cpp): every level is one mixed batch
+// ---------------------------------------------------------------------------
+// The wire store of a run: grow-only; no queued kernel uses the old buffer once sc_fence has passed
+// (every user runs inside a run_device_op frame).  A failed allocation leaves the device without a store
+// and the context usable.
+tfhe_status ensure_wires(Device& d, size_t words) {
+    if (words <= d.wires_words) return TFHE_OK;
+    if (d.sc_fence) HCHECK(hipEventSynchronize(d.sc_fence));
+    hipFree(d.wires);
+    d.wires = nullptr, d.wires_words = 0;
+    HCHECK(hipMalloc(&d.wires, words * sizeof(uint64_t)));
+    d.wires_words = words;
+    return TFHE_OK;
+}
+
+void circuit_plan_free(int device, void* base) {
+    int cur = 0;
+    const bool have = hipGetDevice(&cur) == hipSuccess;
+    if (hipSetDevice(device) == hipSuccess) hipFree(base);  // waits for the kernels still reading it
+    if (have) hipSetDevice(cur);
+}
+
+// The plan arrays of `circ` on HIP device d.id (recs | outs), uploaded on first use and kept with the
+// circuit.  The copies are synchronous: complete before any kernel queued afterwards.
+tfhe_status circuit_plan(const tfhe_circuit* circ, Device& d, const CircuitRec*& recs, const CircuitOut*& outs) {
+    tfhe_circuit* c = const_cast<tfhe_circuit*>(circ);  // the device copies are a cache, not part of the plan
+    std::lock_guard<std::mutex> lock(c->mu);
+    const size_t rb = c->recs.size() * sizeof(CircuitRec), ob = c->outs.size() * sizeof(CircuitOut);
+    void* base = nullptr;
+    for (const tfhe_circuit::DevPlan& p : c->plans)
+        if (p.device == d.id) base = p.base;
+    if (!base) {
+        DevBuf buf;
+        HCHECK(hipMalloc(&buf.p, rb + ob));
+        if (rb) HCHECK(hipMemcpy(buf.p, c->recs.data(), rb, hipMemcpyHostToDevice));
+        HCHECK(hipMemcpy((char*)buf.p + rb, c->outs.data(), ob, hipMemcpyHostToDevice));
+        c->plans.push_back(tfhe_circuit::DevPlan{d.id, buf.p});
+        c->dev_free = circuit_plan_free;
+        base = buf.p;
+        buf.p = nullptr;
+    }
+    recs = static_cast<const CircuitRec*>(base);
+    outs = reinterpret_cast<const CircuitOut*>(static_cast<const char*>(base) + rb);
+    return TFHE_OK;
+}
+
+// trace knob (TFHE_TRACE): event pairs around the launches of the two circuit kernels and the whole run
+struct CircuitTrace {
+    std::vector<hipEvent_t> ev;  // run begin, then (begin, end) per prep launch, (begin, end) per output launch, run end
+    ~CircuitTrace() {
+        for (hipEvent_t e : ev) hipEventDestroy(e);
+    }
+    tfhe_status mark(bool on, hipStream_t s) {
+        if (!on) return TFHE_OK;
+        hipEvent_t e = nullptr;
+        HCHECK(hipEventCreate(&e));
+        ev.push_back(e);
+        HCHECK(hipEventRecord(e, s));
+        return TFHE_OK;
+    }
+};
+
+// One run on one device (inside run_device_op): per level one preparation launch, then the blind rotation,
+// the extraction and the key switch once for the whole mixed level -- in slices of the scratch capacity
+// when width * instances exceeds it; the key switch writes the level's slots of the wire store.
+tfhe_status dev_circuit(tfhe_ctx* c, Device& d, const tfhe_circuit* circ, const CircuitRec* recs,
+                        const CircuitOut* outs, size_t instances, const uint64_t* in, uint64_t q, uint64_t* out) {
+    const tfhe_params& p = c->p;
+    CircuitPrep P{};
+    P.N = p.N, P.n = p.n, P.Q = p.Q, P.Q8 = p.Q / 8 + 1, P.q = q, P.instances = instances;
+    const size_t w = p.n + 1, slice = std::min(d.sc.cap, c->max_chunk);
+    const bool trace = c->kn.trace != 0;
+    CircuitTrace tr;
+    size_t preps = 0;
+    SCHECK(tr.mark(trace, d.stream));
+    for (const CircuitLevel& L : circ->levels) {
+        const size_t total = (size_t)L.width * instances;
+        for (size_t first = 0; first < total; first += slice) {
+            const size_t B = std::min(slice, total - first);
+            P.first = first;
+            SCHECK(tr.mark(trace, d.stream));
+            HCHECK(launch_circuit_prep(P, recs + L.first, in, d.wires, d.sc.acc, d.sc.a, B, d.stream));
+            SCHECK(tr.mark(trace, d.stream));
+            ++preps;
+            SCHECK(dev_blind_rotate(c, d, d.sc.a, q, d.sc.acc, B));
+            HCHECK(launch_extract(p.N, p.Q, P.Q8, d.sc.acc, d.sc.ext, B, d.stream));
+            SCHECK(dev_mkm(c, d, d.sc.ext, q, d.wires + ((size_t)L.first * instances + first) * w, B));
+        }
+    }
+    const size_t total = circ->outs.size() * instances, grid = (size_t)1 << 30;
+    for (size_t first = 0; first < total; first += grid) {
+        P.first = first;
+        SCHECK(tr.mark(trace, d.stream));
+        HCHECK(launch_circuit_out(P, outs, in, d.wires, out, std::min(grid, total - first), d.stream));
+        SCHECK(tr.mark(trace, d.stream));
+    }
+    SCHECK(tr.mark(trace, d.stream));
+    if (trace) {
+        HCHECK(hipStreamSynchronize(d.stream));
+        auto ms = [&](size_t a, size_t b) {
+            float t = 0;
+            hipEventElapsedTime(&t, tr.ev[a], tr.ev[b]);
+            return (double)t;
+        };
+        double prep_ms = 0, out_ms = 0;
+        for (size_t k = 1; k + 1 < tr.ev.size(); k += 2) (k < 1 + 2 * preps ? prep_ms : out_ms) += ms(k, k + 1);
+        std::fprintf(stderr, "[tfhe] circuit: %u bootstraps x %zu instances in %.3f ms; %zu prep launches %.3f ms, output %.3f ms\n",
+                     circ->info.bootstraps, instances, ms(0, tr.ev.size() - 1), preps, prep_ms, out_ms);
+    }
     return TFHE_OK;
 }
 
@@ -1851,6 +1978,65 @@ tfhe_status tfhe_eval_sign_device(tfhe_ctx* c, size_t B, const uint64_t* d_ct, u
         if (B == 0) return TFHE_OK;
         if (!d_ct || !d_out) return fail(TFHE_ERR_INVALID_ARGUMENT, "null argument");
         return run_device_op(c, B, d_out, stream, [&](Device& d) { return dev_sign(c, d, d_ct, mod, d_out, B); });
+    });
+}
+
+extern "C++" {
+namespace {
+tfhe_status check_circuit_call(tfhe_ctx* c, const tfhe_circuit* circ, size_t instances, const void* in, uint64_t q,
+                               const void* out) {
+    SCHECK(check_ctx(c));
+    if (!circ) return fail(TFHE_ERR_INVALID_ARGUMENT, "null circuit");
+    if (instances == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalCircuit: no instances");
+    if (!out || (!in && circ->info.num_inputs > 0)) return fail(TFHE_ERR_INVALID_ARGUMENT, "null argument");
+    if (q == 0 || (2ull * c->p.N) % q != 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "ciphertext modulus must divide 2N");
+    const size_t w = c->p.n + 1, most = std::max<size_t>({circ->info.num_inputs, circ->info.num_outputs, circ->info.bootstraps});
+    if (instances > SIZE_MAX / sizeof(uint64_t) / w / most) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalCircuit: too many instances");
+    return TFHE_OK;
+}
+
+// d_out selects the device; the wire store and the plan are in place before the frame opens
+tfhe_status circuit_on_device(tfhe_ctx* c, const tfhe_circuit* circ, size_t instances, const uint64_t* d_in, uint64_t q,
+                              uint64_t* d_out, void* stream) {
+    Device* dp = nullptr;
+    SCHECK(device_for(c, d_out, dp));
+    HCHECK(hipSetDevice(dp->id));
+    SCHECK(ensure_wires(*dp, (size_t)circ->info.bootstraps * instances * (c->p.n + 1)));
+    const CircuitRec* recs = nullptr;
+    const CircuitOut* outs = nullptr;
+    SCHECK(circuit_plan(circ, *dp, recs, outs));
+    const size_t widest = std::min((size_t)circ->info.widest_level * instances, c->max_chunk);
+    return run_device_op(c, widest, d_out, stream,
+                         [&](Device& d) { return dev_circuit(c, d, circ, recs, outs, instances, d_in, q, d_out); });
+}
+}  // namespace
+}  // extern "C++"
+
+tfhe_status tfhe_eval_circuit_device(tfhe_ctx* c, const tfhe_circuit* circ, size_t instances, const uint64_t* d_in,
+                                     uint64_t q, uint64_t* d_out, void* stream) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_circuit_call(c, circ, instances, d_in, q, d_out));
+        return circuit_on_device(c, circ, instances, d_in, q, d_out, stream);
+    });
+}
+
+tfhe_status tfhe_eval_circuit(tfhe_ctx* c, const tfhe_circuit* circ, size_t instances, const uint64_t* in, uint64_t q,
+                              uint64_t* out) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_circuit_call(c, circ, instances, in, q, out));
+        Device& d = c->devs[0];
+        HCHECK(hipSetDevice(d.id));
+        const size_t w = c->p.n + 1, wi = (size_t)circ->info.num_inputs * instances * w,
+                     wo = (size_t)circ->info.num_outputs * instances * w;
+        DevBuf din, dout;
+        if (wi) HCHECK(hipMalloc(&din.p, wi * sizeof(uint64_t)));
+        HCHECK(hipMalloc(&dout.p, wo * sizeof(uint64_t)));
+        if (wi) SCHECK(h2d_staged(d, din.as<uint64_t>(), flat_rows(in, w), wi, d.stream));
+        tfhe_status st = circuit_on_device(c, circ, instances, din.as<uint64_t>(), q, dout.as<uint64_t>(), nullptr);
+        if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout.as<uint64_t>(), wo, d.stream);
+        const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffers are freed, on every path
+        if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalCircuit: ") + hipGetErrorString(e));
+        return st;
     });
 }
 

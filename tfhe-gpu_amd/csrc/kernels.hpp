@@ -181,6 +181,24 @@ hipError_t launch_narrow(const uint64_t* src, int wb, void* dst, size_t n, hipSt
 hipError_t launch_extract(uint32_t N, uint64_t Q, uint64_t b_add, const uint64_t* acc, uint64_t* ext, size_t B,
                           hipStream_t s);
 
+// ---- circuit path (circuit_kernels.hip; plan records: circuit.hpp) ----
+// One launch covers bootstraps [first, first + B) of a level (or outputs, for launch_circuit_out), flat
+// index = gate * instances + instance; `in` is [num_inputs][instances][n+1], `store` the wire store
+// [bootstraps][instances][n+1].
+struct CircuitRec;
+struct CircuitOut;
+struct CircuitPrep {
+    uint32_t N, n;
+    uint64_t Q, Q8, q;  // Q8 = Q/8 + 1; q: the ciphertext modulus (divides 2N)
+    size_t instances, first;
+};
+// recs: the level's first record.  acc[B][2][N] (acc0 = 0, acc1 = each gate's test vector), a_out[B][n]
+hipError_t launch_circuit_prep(const CircuitPrep& P, const CircuitRec* recs, const uint64_t* in, const uint64_t* store,
+                               uint64_t* acc, uint64_t* a_out, size_t B, hipStream_t s);
+// out[num_outputs][instances][n+1]
+hipError_t launch_circuit_out(const CircuitPrep& P, const CircuitOut* outs, const uint64_t* in, const uint64_t* store,
+                              uint64_t* out, size_t B, hipStream_t s);
+
 enum LweOp : uint32_t {
     LWE_ADD = 0,        // out = x + y mod m
     LWE_SUB = 1,        // out = x - y mod m

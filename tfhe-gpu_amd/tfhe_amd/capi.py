@@ -21,6 +21,7 @@ PARAMSETS = {"TOY": 0, "MEDIUM": 1, "STD128_AP": 2, "STD128_APOPT": 3, "STD128":
              "STD192_OPT": 7, "STD256": 8, "STD256_OPT": 9, "STD128Q": 10, "STD128Q_OPT": 11, "STD192Q": 12,
              "STD192Q_OPT": 13, "STD256Q": 14, "STD256Q_OPT": 15, "SIGNED_MOD_TEST": 16}
 BINGATE = {"OR": 0, "AND": 1, "NOR": 2, "NAND": 3, "XOR_FAST": 4, "XNOR_FAST": 5, "XOR": 6, "XNOR": 7}
+CIRCUIT_OPS = dict(BINGATE, NOT=8, CONST0=9, CONST1=10)  # tfhe_gate + tfhe_circuit_op
 
 
 class TfheError(RuntimeError):
@@ -56,6 +57,18 @@ class Knobs(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("ks_tiled_min", "ks_cts", "ks_split", "ks_pk", "host_parts", "wire",
                                          "acc_flags", "f64w", "sf2", "generic", "trace", "probe", "duo",
                                          "sf2p", "split4", "ks40")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class CircuitGate(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("in0", C.c_uint32), ("in1", C.c_uint32)]
+
+
+class CircuitInfo(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("num_inputs", "num_outputs", "num_gates", "bootstraps", "levels",
+                                          "widest_level")]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -102,6 +115,13 @@ _SIGS = {
     "tfhe_eval_func_device": ([VP, SZ, VP, U64, VP, C.c_int, VP, VP], C.c_int),
     "tfhe_eval_floor_device": ([VP, SZ, VP, U64, C.c_uint32, VP, VP], C.c_int),
     "tfhe_eval_sign_device": ([VP, SZ, VP, U64, VP, VP], C.c_int),
+    "tfhe_circuit_compile": ([C.POINTER(VP), C.c_uint32, VP, SZ, VP, SZ], C.c_int),
+    "tfhe_circuit_free": ([VP], C.c_int),
+    "tfhe_circuit_get_info": ([VP, C.POINTER(CircuitInfo)], C.c_int),
+    "tfhe_circuit_level_widths": ([VP, VP, SZ], C.c_int),
+    "tfhe_circuit_eval_plain": ([VP, SZ, VP, VP], C.c_int),
+    "tfhe_eval_circuit_device": ([VP, VP, SZ, VP, U64, VP, VP], C.c_int),
+    "tfhe_eval_circuit": ([VP, VP, SZ, u64p, U64, u64p], C.c_int),
     "tfhe_export_key_image": ([VP, VP, SZ, VP], C.c_int),
     "tfhe_setup_from_key_image": ([C.POINTER(VP), P, VP, SZ, C.c_int], C.c_int),
     "tfhe_save_key_image": ([VP, C.c_char_p], C.c_int),
