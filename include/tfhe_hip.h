@@ -268,6 +268,68 @@ tfhe_status tfhe_eval_circuit_device(tfhe_ctx* ctx, const tfhe_circuit* c, size_
 tfhe_status tfhe_eval_circuit(tfhe_ctx* ctx, const tfhe_circuit* c, size_t instances, const uint64_t* in, uint64_t q,
                               uint64_t* out);
 
+/* ---- function circuits (no reference counterpart): a netlist over Z_q ciphertext wires whose nodes are linear
+ * forms (free) or programmable bootstraps, each with its own table; compiled once on the host, evaluated on
+ * `instances` independent input sets per call.  Every level runs as ONE mixed batch -- one preparation launch,
+ * one blind rotation, one extraction, one key switch per output modulus -- whatever table classes it mixes.
+ * Results equal tfhe_eval_func (shared table) composed node by node, bit for bit.
+ *
+ * Netlist: wires 0 .. num_inputs-1 are the inputs; node g defines wire num_inputs + g and may read only
+ * lower-numbered wires.  Every node forms v = c0 w[in0] + c1 w[in1] + k mod q: a negative coefficient means
+ * multiplication by q - |c|; c1 == 0 means in1 is ignored; k (< q) is added to b only (EvalAddConstEq).
+ *   TFHE_F_LIN: the wire is v (no bootstrap);
+ *   TFHE_F_LUT: the wire is EvalFunc(v, luts[lut]) (binfhe-base-scheme.cpp:679-924).
+ * luts is [num_luts][q], every entry < q.  A table's class is decided once, at compile time, by the reference's
+ * checkInputFunction (binfhe-base-scheme.cpp:162-186): negacyclic -- one bootstrap; periodic -- two; arbitrary --
+ * two at modulus 2q followed by SetModulus(q).  An output may name any wire.  An unknown op, a forward or
+ * out-of-range wire, a LUT index out of range, a table entry >= q, k >= q, q not a power of two or below 8, no
+ * outputs or a null pointer is TFHE_ERR_INVALID_ARGUMENT, the message naming the node or the table.
+ *
+ * Counts (tfhe_fcircuit_info): bootstraps = #(LUT nodes on negacyclic tables) + 2 #(LUT nodes on the others);
+ * nothing is simplified or removed.  Levels: inputs are level 0 and LIN is transparent (the larger of its
+ * operands' levels; an operand with c1 == 0 does not count).  A one-bootstrap LUT node sits at 1 + its form's
+ * level; a two-bootstrap node has its first stage there and its second stage -- whose level is the node's -- one
+ * level later.  Linear forms are folded at compile time into the bootstraps and outputs that read them, so LIN
+ * nodes take no slot of the wire store, which holds bootstraps * instances * (n+1) words as for tfhe_circuit. */
+typedef enum tfhe_fcircuit_op { TFHE_F_LIN = 0, TFHE_F_LUT = 1 } tfhe_fcircuit_op;
+typedef struct tfhe_fcircuit_node {
+    uint32_t op, in0, in1;
+    int32_t c0, c1;
+    uint32_t lut;            /* TFHE_F_LUT: index into luts; ignored for TFHE_F_LIN */
+    uint64_t k;
+} tfhe_fcircuit_node;
+typedef struct tfhe_fcircuit_info {
+    uint32_t num_inputs, num_outputs, num_nodes;
+    uint32_t bootstraps;     /* per instance, after lowering */
+    uint32_t levels, widest_level;
+    uint32_t num_luts, negacyclic, periodic, arbitrary; /* tables, and tables in each class */
+    uint64_t q;
+} tfhe_fcircuit_info;
+typedef struct tfhe_fcircuit tfhe_fcircuit;
+
+tfhe_status tfhe_fcircuit_compile(tfhe_fcircuit** out, uint32_t num_inputs, const tfhe_fcircuit_node* nodes,
+                                  size_t num_nodes, uint64_t q, const uint64_t* luts, size_t num_luts,
+                                  const uint32_t* outputs, size_t num_outputs);
+/* also releases the plan copies on every device that ran the circuit; no call may be using it.  Live handles are
+ * kept in a registry: a freed (or never compiled) handle is TFHE_ERR_INVALID_ARGUMENT in every tfhe_fcircuit_* /
+ * tfhe_eval_fcircuit* call, a second free included, until a later compile happens to reuse its address. */
+tfhe_status tfhe_fcircuit_free(tfhe_fcircuit* c);
+tfhe_status tfhe_fcircuit_get_info(const tfhe_fcircuit* c, tfhe_fcircuit_info* out);
+/* widths[l] = bootstraps of level l + 1, l < info.levels <= cap */
+tfhe_status tfhe_fcircuit_level_widths(const tfhe_fcircuit* c, uint32_t* widths, size_t cap);
+/* the lowered plan on clear values mod q: in[num_inputs][instances], out[num_outputs][instances] (no GPU);
+ * LIN -> (c0 x + c1 y + k) mod q, LUT -> table[v] */
+tfhe_status tfhe_fcircuit_eval_plain(const tfhe_fcircuit* c, size_t instances, const uint64_t* in, uint64_t* out);
+/* d_in[num_inputs][instances][n+1] mod q -> d_out[num_outputs][instances][n+1], q the circuit's: it must divide
+ * 2N, and a circuit with an arbitrary-class table needs q <= N (TFHE_ERR_UNSUPPORTED otherwise, nothing is
+ * launched).  Device selection, stream ordering and slicing as tfhe_eval_circuit_device; tfhe_info.bootstraps
+ * grows by info.bootstraps * instances. */
+tfhe_status tfhe_eval_fcircuit_device(tfhe_ctx* ctx, const tfhe_fcircuit* c, size_t instances, const uint64_t* d_in,
+                                      uint64_t* d_out, void* stream);
+/* the same on host arrays, staged through the context's first device */
+tfhe_status tfhe_eval_fcircuit(tfhe_ctx* ctx, const tfhe_fcircuit* c, size_t instances, const uint64_t* in,
+                               uint64_t* out);
+
 /* ---- key replication for one-process-per-GPU deployments ----
  * The packed device key image (NTT-domain BSK with Shoup companions, packed
  * KSK, tables) can be copied device-to-device (e.g. broadcast over RCCL/xGMI by

@@ -43,17 +43,6 @@ struct Boot {
 
 tfhe_status bad(const std::string& msg) { return set_last_error(TFHE_ERR_INVALID_ARGUMENT, "tfhe_circuit_compile: " + msg); }
 
-template <typename F>
-tfhe_status guarded(F&& body) {
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        return set_last_error(TFHE_ERR_OUT_OF_MEMORY, "host allocation failed");
-    } catch (const std::exception& e) {
-        return set_last_error(TFHE_ERR_INTERNAL, std::string("internal error: ") + e.what());
-    }
-}
-
 inline uint8_t gate_bit(uint32_t op, uint8_t x, uint8_t y) {
     switch (op) {
         case TFHE_OR: return x | y;
@@ -71,7 +60,7 @@ extern "C" {
 
 tfhe_status tfhe_circuit_compile(tfhe_circuit** out, uint32_t num_inputs, const tfhe_circuit_gate* gates,
                                  size_t num_gates, const uint32_t* outputs, size_t num_outputs) {
-    return guarded([&]() -> tfhe_status {
+    return host_guarded([&]() -> tfhe_status {
         if (!out) return bad("null output pointer");
         *out = nullptr;
         if (num_gates > 0 && !gates) return bad("null gate array with num_gates > 0");
@@ -166,8 +155,7 @@ tfhe_status tfhe_circuit_compile(tfhe_circuit** out, uint32_t num_inputs, const 
 
 tfhe_status tfhe_circuit_free(tfhe_circuit* c) {
     if (!c) return TFHE_OK;
-    for (const tfhe_circuit::DevPlan& p : c->plans)
-        if (c->dev_free) c->dev_free(p.device, p.base);
+    c->cache.release();
     delete c;
     return TFHE_OK;
 }
@@ -190,7 +178,7 @@ tfhe_status tfhe_circuit_level_widths(const tfhe_circuit* c, uint32_t* widths, s
 }
 
 tfhe_status tfhe_circuit_eval_plain(const tfhe_circuit* c, size_t instances, const uint8_t* in, uint8_t* out) {
-    return guarded([&]() -> tfhe_status {
+    return host_guarded([&]() -> tfhe_status {
         if (!c || !out || (!in && c->info.num_inputs > 0 && instances > 0))
             return set_last_error(TFHE_ERR_INVALID_ARGUMENT, "tfhe_circuit_eval_plain: null argument");
         std::vector<uint8_t> store(c->recs.size() * instances);

@@ -10,7 +10,9 @@
 #pragma once
 
 #include <cstdint>
+#include <exception>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -45,16 +47,22 @@ struct CircuitLevel {
 // last-error channel of the C-ABI (engine.hip); returns s
 tfhe_status set_last_error(tfhe_status s, const std::string& msg);
 
-}  // namespace tfhe
+// exceptions of a host-only entry point -> status + last error
+template <typename F>
+tfhe_status host_guarded(F&& body) {
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return set_last_error(TFHE_ERR_OUT_OF_MEMORY, "host allocation failed");
+    } catch (const std::exception& e) {
+        return set_last_error(TFHE_ERR_INTERNAL, std::string("internal error: ") + e.what());
+    }
+}
 
-struct tfhe_circuit {
-    tfhe_circuit_info info{};
-    std::vector<tfhe::CircuitRec> recs;      // [bootstraps], slot order
-    std::vector<tfhe::CircuitLevel> levels;  // [info.levels]
-    std::vector<tfhe::CircuitOut> outs;      // [num_outputs]
-    // Device copies of recs | outs (outs at byte offset recs.size() * 16), one per HIP device that ran
-    // the circuit; uploaded by engine.hip on first use, released through dev_free (set by the uploader;
-    // this file has no HIP dependency) in tfhe_circuit_free.
+// Device copies of a compiled plan (one byte image), one per HIP device that ran the circuit; uploaded by
+// engine.hip on first use (plan_on_device), released through dev_free (set by the uploader; the compilers have
+// no HIP dependency) when the circuit is freed.
+struct PlanCache {
     struct DevPlan {
         int device;
         void* base;
@@ -62,4 +70,19 @@ struct tfhe_circuit {
     std::mutex mu;
     std::vector<DevPlan> plans;
     void (*dev_free)(int device, void* base) = nullptr;
+    void release() {
+        for (const DevPlan& p : plans)
+            if (dev_free) dev_free(p.device, p.base);
+        plans.clear();
+    }
+};
+
+}  // namespace tfhe
+
+struct tfhe_circuit {
+    tfhe_circuit_info info{};
+    std::vector<tfhe::CircuitRec> recs;      // [bootstraps], slot order
+    std::vector<tfhe::CircuitLevel> levels;  // [info.levels]
+    std::vector<tfhe::CircuitOut> outs;      // [num_outputs]
+    tfhe::PlanCache cache;  // device copies of recs | outs (outs at byte offset recs.size() * 16)
 };

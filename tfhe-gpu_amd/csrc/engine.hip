@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "circuit.hpp"
+#include "fcircuit.hpp"
 #include "duo.hpp"
 #include "host_math.hpp"
 #include "kernels.hpp"
@@ -660,22 +661,6 @@ tfhe_status dev_gate(tfhe_ctx* c, Device& d, int gate, const uint64_t* ct1, cons
     return dev_bootstrap(c, d, tv, c->p.Q / 8 + 1, prep, out, B);
 }
 
-// binfhe-base-scheme.cpp:162-186
-int check_input_function(const uint64_t* lut, uint64_t len, uint64_t mod) {
-    const uint64_t h = len / 2;
-    if (lut[0] == mod - lut[h]) {
-        for (uint64_t i = 1; i < h; ++i)
-            if (lut[i] != mod - lut[h + i]) return 2;
-        return 0;
-    }
-    if (lut[0] == lut[h]) {
-        for (uint64_t i = 1; i < h; ++i)
-            if (lut[i] != lut[h + i]) return 2;
-        return 1;
-    }
-    return 2;
-}
-
 // vector EvalFunc, binfhe-base-scheme.cpp:679-924.  d_lut is a device LUT ([q] or [B][q]).
 tfhe_status dev_func(tfhe_ctx* c, Device& d, int prop, const uint64_t* ct, uint64_t q, const uint64_t* d_lut,
                      uint64_t lut_stride, uint64_t* out, size_t B) {
@@ -792,27 +777,44 @@ void circuit_plan_free(int device, void* base) {
     if (have) hipSetDevice(cur);
 }
 
-// The plan arrays of `circ` on HIP device d.id (recs | outs), uploaded on first use and kept with the
-// circuit.  The copies are synchronous: complete before any kernel queued afterwards.
-tfhe_status circuit_plan(const tfhe_circuit* circ, Device& d, const CircuitRec*& recs, const CircuitOut*& outs) {
-    tfhe_circuit* c = const_cast<tfhe_circuit*>(circ);  // the device copies are a cache, not part of the plan
-    std::lock_guard<std::mutex> lock(c->mu);
-    const size_t rb = c->recs.size() * sizeof(CircuitRec), ob = c->outs.size() * sizeof(CircuitOut);
+// A compiled plan's arrays on HIP device d.id, one after the other in `parts` order (every part's size is a
+// multiple of 8 bytes), uploaded on first use and kept with the circuit.  The copies are synchronous: complete
+// before any kernel queued afterwards.
+struct PlanPart {
+    const void* p;
+    size_t bytes;
+};
+tfhe_status plan_on_device(PlanCache& cache, Device& d, std::initializer_list<PlanPart> parts, const char*& base_out) {
+    std::lock_guard<std::mutex> lock(cache.mu);
     void* base = nullptr;
-    for (const tfhe_circuit::DevPlan& p : c->plans)
+    for (const PlanCache::DevPlan& p : cache.plans)
         if (p.device == d.id) base = p.base;
     if (!base) {
+        size_t total = 0;
+        for (const PlanPart& part : parts) total += part.bytes;
         DevBuf buf;
-        HCHECK(hipMalloc(&buf.p, rb + ob));
-        if (rb) HCHECK(hipMemcpy(buf.p, c->recs.data(), rb, hipMemcpyHostToDevice));
-        HCHECK(hipMemcpy((char*)buf.p + rb, c->outs.data(), ob, hipMemcpyHostToDevice));
-        c->plans.push_back(tfhe_circuit::DevPlan{d.id, buf.p});
-        c->dev_free = circuit_plan_free;
+        HCHECK(hipMalloc(&buf.p, std::max<size_t>(total, 8)));
+        size_t at = 0;
+        for (const PlanPart& part : parts) {
+            if (part.bytes) HCHECK(hipMemcpy((char*)buf.p + at, part.p, part.bytes, hipMemcpyHostToDevice));
+            at += part.bytes;
+        }
+        cache.plans.push_back(PlanCache::DevPlan{d.id, buf.p});
+        cache.dev_free = circuit_plan_free;
         base = buf.p;
         buf.p = nullptr;
     }
-    recs = static_cast<const CircuitRec*>(base);
-    outs = reinterpret_cast<const CircuitOut*>(static_cast<const char*>(base) + rb);
+    base_out = static_cast<const char*>(base);
+    return TFHE_OK;
+}
+
+tfhe_status circuit_plan(const tfhe_circuit* circ, Device& d, const CircuitRec*& recs, const CircuitOut*& outs) {
+    tfhe_circuit* c = const_cast<tfhe_circuit*>(circ);  // the device copies are a cache, not part of the plan
+    const size_t rb = c->recs.size() * sizeof(CircuitRec), ob = c->outs.size() * sizeof(CircuitOut);
+    const char* base = nullptr;
+    SCHECK(plan_on_device(c->cache, d, {{c->recs.data(), rb}, {c->outs.data(), ob}}, base));
+    recs = reinterpret_cast<const CircuitRec*>(base);
+    outs = reinterpret_cast<const CircuitOut*>(base + rb);
     return TFHE_OK;
 }
 
@@ -828,6 +830,20 @@ struct CircuitTrace {
         HCHECK(hipEventCreate(&e));
         ev.push_back(e);
         HCHECK(hipEventRecord(e, s));
+        return TFHE_OK;
+    }
+    // after the run-end mark: waits for the stream and prints the circuit line
+    tfhe_status report(hipStream_t s, uint32_t bootstraps, size_t instances, size_t preps) {
+        HCHECK(hipStreamSynchronize(s));
+        auto ms = [&](size_t a, size_t b) {
+            float t = 0;
+            hipEventElapsedTime(&t, ev[a], ev[b]);
+            return (double)t;
+        };
+        double prep_ms = 0, out_ms = 0;
+        for (size_t k = 1; k + 1 < ev.size(); k += 2) (k < 1 + 2 * preps ? prep_ms : out_ms) += ms(k, k + 1);
+        std::fprintf(stderr, "[tfhe] circuit: %u bootstraps x %zu instances in %.3f ms; %zu prep launches %.3f ms, output %.3f ms\n",
+                     bootstraps, instances, ms(0, ev.size() - 1), preps, prep_ms, out_ms);
         return TFHE_OK;
     }
 };
@@ -867,18 +883,73 @@ tfhe_status dev_circuit(tfhe_ctx* c, Device& d, const tfhe_circuit* circ, const 
         SCHECK(tr.mark(trace, d.stream));
     }
     SCHECK(tr.mark(trace, d.stream));
-    if (trace) {
-        HCHECK(hipStreamSynchronize(d.stream));
-        auto ms = [&](size_t a, size_t b) {
-            float t = 0;
-            hipEventElapsedTime(&t, tr.ev[a], tr.ev[b]);
-            return (double)t;
-        };
-        double prep_ms = 0, out_ms = 0;
-        for (size_t k = 1; k + 1 < tr.ev.size(); k += 2) (k < 1 + 2 * preps ? prep_ms : out_ms) += ms(k, k + 1);
-        std::fprintf(stderr, "[tfhe] circuit: %u bootstraps x %zu instances in %.3f ms; %zu prep launches %.3f ms, output %.3f ms\n",
-                     circ->info.bootstraps, instances, ms(0, tr.ev.size() - 1), preps, prep_ms, out_ms);
+    if (trace) SCHECK(tr.report(d.stream, circ->info.bootstraps, instances, preps));
+    return TFHE_OK;
+}
+
+// The plan of a function circuit on one device (plan_on_device order: recs | terms | outs | luts).
+struct FuncPlan {
+    const FuncRec* recs;
+    const FuncTerm* terms;
+    const FuncOut* outs;
+    const uint64_t* luts;
+};
+tfhe_status fcircuit_plan(const tfhe_fcircuit* circ, Device& d, FuncPlan& pl) {
+    tfhe_fcircuit* c = const_cast<tfhe_fcircuit*>(circ);  // the device copies are a cache, not part of the plan
+    const size_t rb = c->recs.size() * sizeof(FuncRec), tb = c->terms.size() * sizeof(FuncTerm),
+                 ob = c->outs.size() * sizeof(FuncOut), lb = c->luts.size() * sizeof(uint64_t);
+    const char* base = nullptr;
+    SCHECK(plan_on_device(c->cache, d, {{c->recs.data(), rb}, {c->terms.data(), tb}, {c->outs.data(), ob}, {c->luts.data(), lb}},
+                          base));
+    pl.recs = reinterpret_cast<const FuncRec*>(base);
+    pl.terms = reinterpret_cast<const FuncTerm*>(base + rb);
+    pl.outs = reinterpret_cast<const FuncOut*>(base + rb + tb);
+    pl.luts = reinterpret_cast<const uint64_t*>(base + rb + tb + ob);
+    return TFHE_OK;
+}
+
+// One run of a function circuit on one device (inside run_device_op): per level (or slice) one preparation
+// launch, ONE blind rotation at a-modulus 2N for records of both ciphertext moduli (the preparation kernel
+// scales every mask to 2N), one extraction, and the key switch once per output modulus: the records that end
+// at q are the level's first width_q slots, those that end at 2q the rest, so each call writes one contiguous
+// range of the wire store.
+tfhe_status dev_fcircuit(tfhe_ctx* c, Device& d, const tfhe_fcircuit* circ, const FuncPlan& pl, size_t instances,
+                         const uint64_t* in, uint64_t* out) {
+    const tfhe_params& p = c->p;
+    const uint64_t q = circ->info.q;
+    FuncPrep P{};
+    P.N = p.N, P.n = p.n, P.log2N = ilog2(p.N), P.Q = p.Q, P.q = q, P.instances = instances;
+    const size_t w = p.n + 1, slice = std::min(d.sc.cap, c->max_chunk);
+    const bool trace = c->kn.trace != 0;
+    CircuitTrace tr;
+    size_t preps = 0;
+    SCHECK(tr.mark(trace, d.stream));
+    for (const FuncLevel& L : circ->levels) {
+        const size_t total = (size_t)L.width * instances, at_q = (size_t)L.width_q * instances;
+        for (size_t first = 0; first < total; first += slice) {
+            const size_t B = std::min(slice, total - first);
+            P.first = first;
+            SCHECK(tr.mark(trace, d.stream));
+            HCHECK(launch_fcircuit_prep(P, pl.recs + L.first, pl.terms, pl.luts, in, d.wires, d.sc.acc, d.sc.a, B, d.stream));
+            SCHECK(tr.mark(trace, d.stream));
+            ++preps;
+            SCHECK(dev_blind_rotate(c, d, d.sc.a, 2ull * p.N, d.sc.acc, B));
+            HCHECK(launch_extract(p.N, p.Q, 0, d.sc.acc, d.sc.ext, B, d.stream));
+            const size_t nq = at_q > first ? std::min(B, at_q - first) : 0;  // of this slice, those that end at q
+            uint64_t* dst = d.wires + ((size_t)L.first * instances + first) * w;
+            if (nq) SCHECK(dev_mkm(c, d, d.sc.ext, q, dst, nq));
+            if (B > nq) SCHECK(dev_mkm(c, d, d.sc.ext + nq * ((size_t)p.N + 1), q << 1, dst + nq * w, B - nq));
+        }
     }
+    const size_t total = circ->outs.size() * instances, grid = (size_t)1 << 30;
+    for (size_t first = 0; first < total; first += grid) {
+        P.first = first;
+        SCHECK(tr.mark(trace, d.stream));
+        HCHECK(launch_fcircuit_out(P, pl.outs, pl.terms, in, d.wires, out, std::min(grid, total - first), d.stream));
+        SCHECK(tr.mark(trace, d.stream));
+    }
+    SCHECK(tr.mark(trace, d.stream));
+    if (trace) SCHECK(tr.report(d.stream, circ->info.bootstraps, instances, preps));
     return TFHE_OK;
 }
 
@@ -1983,16 +2054,63 @@ tfhe_status tfhe_eval_sign_device(tfhe_ctx* c, size_t B, const uint64_t* d_ct, u
 
 extern "C++" {
 namespace {
+// what both circuit kinds check of a call (after the context and the circuit handle)
+tfhe_status check_circuit_shape(tfhe_ctx* c, uint32_t num_inputs, uint32_t num_outputs, uint32_t bootstraps,
+                                size_t instances, const void* in, uint64_t q, const void* out) {
+    if (instances == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalCircuit: no instances");
+    if (!out || (!in && num_inputs > 0)) return fail(TFHE_ERR_INVALID_ARGUMENT, "null argument");
+    if (q == 0 || (2ull * c->p.N) % q != 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "ciphertext modulus must divide 2N");
+    const size_t w = c->p.n + 1, most = std::max<size_t>({num_inputs, num_outputs, bootstraps});
+    if (instances > SIZE_MAX / sizeof(uint64_t) / w / most) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalCircuit: too many instances");
+    return TFHE_OK;
+}
+
 tfhe_status check_circuit_call(tfhe_ctx* c, const tfhe_circuit* circ, size_t instances, const void* in, uint64_t q,
                                const void* out) {
     SCHECK(check_ctx(c));
     if (!circ) return fail(TFHE_ERR_INVALID_ARGUMENT, "null circuit");
-    if (instances == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalCircuit: no instances");
-    if (!out || (!in && circ->info.num_inputs > 0)) return fail(TFHE_ERR_INVALID_ARGUMENT, "null argument");
-    if (q == 0 || (2ull * c->p.N) % q != 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "ciphertext modulus must divide 2N");
-    const size_t w = c->p.n + 1, most = std::max<size_t>({circ->info.num_inputs, circ->info.num_outputs, circ->info.bootstraps});
-    if (instances > SIZE_MAX / sizeof(uint64_t) / w / most) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalCircuit: too many instances");
+    return check_circuit_shape(c, circ->info.num_inputs, circ->info.num_outputs, circ->info.bootstraps, instances, in, q, out);
+}
+
+tfhe_status check_fcircuit_call(tfhe_ctx* c, const tfhe_fcircuit* circ, size_t instances, const void* in, const void* out) {
+    SCHECK(check_ctx(c));
+    if (!fcircuit_alive(circ)) return fail(TFHE_ERR_INVALID_ARGUMENT, "null, freed or unknown function circuit");
+    const tfhe_fcircuit_info& I = circ->info;
+    SCHECK(check_circuit_shape(c, I.num_inputs, I.num_outputs, I.bootstraps, instances, in, I.q, out));
+    if (I.arbitrary > 0 && I.q > c->p.N) return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
     return TFHE_OK;
+}
+
+// the host-array form of both circuit kinds: staged through the context's first device around on_device(d_in, d_out)
+template <typename F>
+tfhe_status circuit_from_host(tfhe_ctx* c, uint32_t num_inputs, uint32_t num_outputs, size_t instances, const uint64_t* in,
+                              uint64_t* out, F&& on_device) {
+    Device& d = c->devs[0];
+    HCHECK(hipSetDevice(d.id));
+    const size_t w = c->p.n + 1, wi = (size_t)num_inputs * instances * w, wo = (size_t)num_outputs * instances * w;
+    DevBuf din, dout;
+    if (wi) HCHECK(hipMalloc(&din.p, wi * sizeof(uint64_t)));
+    HCHECK(hipMalloc(&dout.p, wo * sizeof(uint64_t)));
+    if (wi) SCHECK(h2d_staged(d, din.as<uint64_t>(), flat_rows(in, w), wi, d.stream));
+    tfhe_status st = on_device(din.as<uint64_t>(), dout.as<uint64_t>());
+    if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout.as<uint64_t>(), wo, d.stream);
+    const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffers are freed, on every path
+    if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalCircuit: ") + hipGetErrorString(e));
+    return st;
+}
+
+// d_out selects the device; the wire store and the plan are in place before the frame opens
+tfhe_status fcircuit_on_device(tfhe_ctx* c, const tfhe_fcircuit* circ, size_t instances, const uint64_t* d_in,
+                               uint64_t* d_out, void* stream) {
+    Device* dp = nullptr;
+    SCHECK(device_for(c, d_out, dp));
+    HCHECK(hipSetDevice(dp->id));
+    SCHECK(ensure_wires(*dp, (size_t)circ->info.bootstraps * instances * (c->p.n + 1)));
+    FuncPlan pl{};
+    SCHECK(fcircuit_plan(circ, *dp, pl));
+    const size_t widest = std::min((size_t)circ->info.widest_level * instances, c->max_chunk);
+    return run_device_op(c, widest, d_out, stream,
+                         [&](Device& d) { return dev_fcircuit(c, d, circ, pl, instances, d_in, d_out); });
 }
 
 // d_out selects the device; the wire store and the plan are in place before the frame opens
@@ -2024,19 +2142,29 @@ tfhe_status tfhe_eval_circuit(tfhe_ctx* c, const tfhe_circuit* circ, size_t inst
                               uint64_t* out) {
     return guarded([&]() -> tfhe_status {
         SCHECK(check_circuit_call(c, circ, instances, in, q, out));
-        Device& d = c->devs[0];
-        HCHECK(hipSetDevice(d.id));
-        const size_t w = c->p.n + 1, wi = (size_t)circ->info.num_inputs * instances * w,
-                     wo = (size_t)circ->info.num_outputs * instances * w;
-        DevBuf din, dout;
-        if (wi) HCHECK(hipMalloc(&din.p, wi * sizeof(uint64_t)));
-        HCHECK(hipMalloc(&dout.p, wo * sizeof(uint64_t)));
-        if (wi) SCHECK(h2d_staged(d, din.as<uint64_t>(), flat_rows(in, w), wi, d.stream));
-        tfhe_status st = circuit_on_device(c, circ, instances, din.as<uint64_t>(), q, dout.as<uint64_t>(), nullptr);
-        if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout.as<uint64_t>(), wo, d.stream);
-        const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffers are freed, on every path
-        if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalCircuit: ") + hipGetErrorString(e));
-        return st;
+        return circuit_from_host(c, circ->info.num_inputs, circ->info.num_outputs, instances, in, out,
+                                 [&](const uint64_t* d_in, uint64_t* d_out) {
+                                     return circuit_on_device(c, circ, instances, d_in, q, d_out, nullptr);
+                                 });
+    });
+}
+
+tfhe_status tfhe_eval_fcircuit_device(tfhe_ctx* c, const tfhe_fcircuit* circ, size_t instances, const uint64_t* d_in,
+                                      uint64_t* d_out, void* stream) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_fcircuit_call(c, circ, instances, d_in, d_out));
+        return fcircuit_on_device(c, circ, instances, d_in, d_out, stream);
+    });
+}
+
+tfhe_status tfhe_eval_fcircuit(tfhe_ctx* c, const tfhe_fcircuit* circ, size_t instances, const uint64_t* in,
+                               uint64_t* out) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_fcircuit_call(c, circ, instances, in, out));
+        return circuit_from_host(c, circ->info.num_inputs, circ->info.num_outputs, instances, in, out,
+                                 [&](const uint64_t* d_in, uint64_t* d_out) {
+                                     return fcircuit_on_device(c, circ, instances, d_in, d_out, nullptr);
+                                 });
     });
 }
 

@@ -199,6 +199,26 @@ hipError_t launch_circuit_prep(const CircuitPrep& P, const CircuitRec* recs, con
 hipError_t launch_circuit_out(const CircuitPrep& P, const CircuitOut* outs, const uint64_t* in, const uint64_t* store,
                               uint64_t* out, size_t B, hipStream_t s);
 
+// ---- function-circuit path (fcircuit_kernels.hip; plan records: fcircuit.hpp) ----
+// As above with flat index = record * instances + instance.  q: the circuit's modulus, a power of two that
+// divides 2N (records at 2q need q <= N); N = 2^log2N.
+struct FuncRec;
+struct FuncTerm;
+struct FuncOut;
+struct FuncPrep {
+    uint32_t N, n, log2N;
+    uint64_t Q, q;
+    size_t instances, first;
+};
+// recs: the level's first record; terms / luts: the plan's.  acc[B][2][N] (acc0 = 0, acc1 = each record's test
+// vector), a_out[B][n] = each mask scaled to modulus 2N
+hipError_t launch_fcircuit_prep(const FuncPrep& P, const FuncRec* recs, const FuncTerm* terms, const uint64_t* luts,
+                                const uint64_t* in, const uint64_t* store, uint64_t* acc, uint64_t* a_out, size_t B,
+                                hipStream_t s);
+// out[num_outputs][instances][n+1]
+hipError_t launch_fcircuit_out(const FuncPrep& P, const FuncOut* outs, const FuncTerm* terms, const uint64_t* in,
+                               const uint64_t* store, uint64_t* out, size_t B, hipStream_t s);
+
 enum LweOp : uint32_t {
     LWE_ADD = 0,        // out = x + y mod m
     LWE_SUB = 1,        // out = x - y mod m

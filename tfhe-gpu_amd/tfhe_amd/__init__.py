@@ -5,14 +5,16 @@ The engine is the C-ABI shared library built from ``tfhe-gpu_amd/csrc`` (see
 and mirrors the vector ``BinFHEContext`` surface of the reference
 (binfhecontext.cpp:316-365): ``GPUSetup``, ``EvalBinGate``, ``EvalFunc``,
 ``EvalFloor``, ``EvalSign``, ``EvalDecomp``, plus the low-level
-``EvalAcc``/``MKMSwitch`` boundary calls, and ``Circuit`` / ``EvalCircuit``:
-a netlist of mixed gates evaluated level by level on the device.  There is no CPU fallback: if the
+``EvalAcc``/``MKMSwitch`` boundary calls, ``Circuit`` / ``EvalCircuit``:
+a netlist of mixed gates evaluated level by level on the device, and ``FuncCircuit`` / ``EvalFuncCircuit``: the
+same for netlists of linear forms and LUT bootstraps over Z_q.  There is no CPU fallback: if the
 library or a GPU is missing, calls raise.
 """
-from .capi import (BINGATE, CIRCUIT_OPS, PARAMSETS, TfheError, Params, lib, library_path, build, exported_symbols,
+from .capi import (BINGATE, CIRCUIT_OPS, FCIRCUIT_OPS, PARAMSETS, TfheError, Params, lib, library_path, build, exported_symbols,
                    params_from_set, params_from_logq, host_selftest)
 from .circuit import Circuit
+from .fcircuit import FuncCircuit
 from .context import BinFHEContextHIP
 
-__all__ = ["BINGATE", "CIRCUIT_OPS", "Circuit", "PARAMSETS", "TfheError", "Params", "lib", "library_path", "build", "exported_symbols",
+__all__ = ["BINGATE", "CIRCUIT_OPS", "Circuit", "FCIRCUIT_OPS", "FuncCircuit", "PARAMSETS", "TfheError", "Params", "lib", "library_path", "build", "exported_symbols",
            "params_from_set", "params_from_logq", "host_selftest", "BinFHEContextHIP"]

@@ -22,6 +22,7 @@ PARAMSETS = {"TOY": 0, "MEDIUM": 1, "STD128_AP": 2, "STD128_APOPT": 3, "STD128":
              "STD192Q_OPT": 13, "STD256Q": 14, "STD256Q_OPT": 15, "SIGNED_MOD_TEST": 16}
 BINGATE = {"OR": 0, "AND": 1, "NOR": 2, "NAND": 3, "XOR_FAST": 4, "XNOR_FAST": 5, "XOR": 6, "XNOR": 7}
 CIRCUIT_OPS = dict(BINGATE, NOT=8, CONST0=9, CONST1=10)  # tfhe_gate + tfhe_circuit_op
+FCIRCUIT_OPS = {"LIN": 0, "LUT": 1}  # tfhe_fcircuit_op
 
 
 class TfheError(RuntimeError):
@@ -69,6 +70,20 @@ class CircuitGate(C.Structure):
 class CircuitInfo(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("num_inputs", "num_outputs", "num_gates", "bootstraps", "levels",
                                           "widest_level")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FuncNode(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("in0", C.c_uint32), ("in1", C.c_uint32), ("c0", C.c_int32), ("c1", C.c_int32),
+                ("lut", C.c_uint32), ("k", C.c_uint64)]
+
+
+class FuncCircuitInfo(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("num_inputs", "num_outputs", "num_nodes", "bootstraps", "levels",
+                                          "widest_level", "num_luts", "negacyclic", "periodic", "arbitrary")] + \
+               [("q", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -122,6 +137,13 @@ _SIGS = {
     "tfhe_circuit_eval_plain": ([VP, SZ, VP, VP], C.c_int),
     "tfhe_eval_circuit_device": ([VP, VP, SZ, VP, U64, VP, VP], C.c_int),
     "tfhe_eval_circuit": ([VP, VP, SZ, u64p, U64, u64p], C.c_int),
+    "tfhe_fcircuit_compile": ([C.POINTER(VP), C.c_uint32, VP, SZ, U64, VP, SZ, VP, SZ], C.c_int),
+    "tfhe_fcircuit_free": ([VP], C.c_int),
+    "tfhe_fcircuit_get_info": ([VP, C.POINTER(FuncCircuitInfo)], C.c_int),
+    "tfhe_fcircuit_level_widths": ([VP, VP, SZ], C.c_int),
+    "tfhe_fcircuit_eval_plain": ([VP, SZ, VP, VP], C.c_int),
+    "tfhe_eval_fcircuit_device": ([VP, VP, SZ, VP, VP, VP], C.c_int),
+    "tfhe_eval_fcircuit": ([VP, VP, SZ, u64p, u64p], C.c_int),
     "tfhe_export_key_image": ([VP, VP, SZ, VP], C.c_int),
     "tfhe_setup_from_key_image": ([C.POINTER(VP), P, VP, SZ, C.c_int], C.c_int),
     "tfhe_save_key_image": ([VP, C.c_char_p], C.c_int),

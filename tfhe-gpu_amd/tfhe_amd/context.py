@@ -235,6 +235,29 @@ class BinFHEContextHIP:
                                                      q or self.params.q, C.c_void_p(d_out), C.c_void_p(stream)),
                     "tfhe_eval_circuit_device")
 
+    # -- function circuits (tfhe_amd.FuncCircuit): linear forms and LUT bootstraps, every level one mixed batch --
+    def EvalFuncCircuit(self, fc, cts):
+        """cts[num_inputs, instances, n+1] mod the circuit's q (or [num_inputs, n+1]: one instance) -> the outputs
+        in the matching shape; host arrays staged through the context's first device."""
+        inf, w = fc.info(), self.params.n + 1
+        x = _u64(cts)
+        one = x.ndim == 2
+        if one:
+            x = x[:, None, :]
+        if x.ndim != 3 or x.shape[0] != inf["num_inputs"] or x.shape[2] != w or x.shape[1] == 0:
+            raise ValueError(f"EvalFuncCircuit: expected shape ({inf['num_inputs']}, instances, {w}), got {x.shape}")
+        x = np.ascontiguousarray(x)
+        out = np.empty((inf["num_outputs"], x.shape[1], w), dtype=np.uint64)
+        self._check(self._L.tfhe_eval_fcircuit(self._h, fc.handle, x.shape[1], x.ravel(), out.ravel()),
+                    "tfhe_eval_fcircuit")
+        return out[:, 0, :] if one else out
+
+    def EvalFuncCircuitDevice(self, fc, instances, d_in, d_out, stream=0):
+        """d_in[num_inputs][instances][n+1] -> d_out[num_outputs][instances][n+1], device pointers."""
+        self._check(self._L.tfhe_eval_fcircuit_device(self._h, fc.handle, instances, C.c_void_p(d_in),
+                                                      C.c_void_p(d_out), C.c_void_p(stream)),
+                    "tfhe_eval_fcircuit_device")
+
     # -- device-resident (pointers are integers, e.g. torch tensor.data_ptr()) --
     def EvalBinGateDevice(self, gate, B, d_ct1, d_ct2, d_out, q=None, stream=0):
         g = BINGATE[gate] if isinstance(gate, str) else int(gate)
