@@ -330,6 +330,62 @@ tfhe_status tfhe_eval_fcircuit_device(tfhe_ctx* ctx, const tfhe_fcircuit* c, siz
 tfhe_status tfhe_eval_fcircuit(tfhe_ctx* ctx, const tfhe_fcircuit* c, size_t instances, const uint64_t* in,
                                uint64_t* out);
 
+/* ---- key generation, encryption and decryption on the device (no reference counterpart; new symbols only, the
+ * ABI version stays) ----
+ * FOR TESTS, BENCHMARKS AND REPRODUCIBLE EXPERIMENTS.  The generator is splitmix64 from a 64-bit seed: it
+ * reproduces this project's CPU oracle word for word and is NOT a cryptographic generator.  Production keys
+ * come from the client's OpenFHE through tfhe_setup_eval.
+ *
+ * The stream.  `seed` is the generator state: draw k (k = 0, 1, ...) is mix(seed + (k + 1) g),
+ * g = 0x9E3779B97F4A7C15, mix(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ * z ^ z >> 31.  Every word of a key sits at a fixed draw, so rows are generated independently.
+ *   uniform(m) = draw mod m;   ternary = draw mod 3 - 1;
+ *   gauss (two draws d, d'): u1 = ((d >> 11) + 1.0) / 9007199254740993.0, u2 = (d' >> 11) / 9007199254740992.0,
+ *     llround(3.19 * (sqrt(-2 log u1) * cos(6.283185307179586 * u2))), every product rounded on its own
+ *     (IEEE double, no fused multiply-add); log and cos are the device library's.
+ * Order of a key generation:
+ *   1. s: n ternaries (sk = s mod qKS);   2. sN: N ternaries;
+ *   3. KSK rows in (i, j, k) order, row r at draw n + N + r (n + 2): its gauss e, then n uniforms mod qKS (A);
+ *      B = e + sN[i] j baseKS^k + <A, s> mod qKS at index n;
+ *   4. BSK rows in (i, key, row) order behind all KSK rows, row r at offset 3 N r: N uniforms mod Q (a), then N
+ *      gauss (e); b = a sN + e in Z_Q[X]/(X^N + 1); when the row's message bit is set (key 0: s_i = 1; key 1:
+ *      s_i = -1), baseG^((row >> 1) + numDigitsToThrow) is added to coefficient 0 of a (even row) or b (odd row).
+ *   The state after the keys is seed + (n + N + rows_KSK (n + 2) + rows_BSK 3 N) g.
+ * Encryption of ciphertext b of a call reads draws b (n + 2) ...: its gauss e, then n uniforms mod `mod` (a);
+ *   b = (m mod ptxt_mod) (mod / ptxt_mod) + e + <a, s> mod `mod`, m mod ptxt_mod taken non-negative, s switched
+ *   from qKS to `mod` by its centred value; B ciphertexts advance the state by B (n + 2) g -- B successive
+ *   single encryptions.  Decryption: r = b - <a, s> + mod / (2 ptxt_mod) mod `mod`; m = floor(ptxt_mod r / mod).
+ *
+ * Argument errors -- a null pointer (the optional ones are named below), B = 0, mod = 0, ptxt_mod = 0 or
+ * ptxt_mod > mod, parameters tfhe_params_finish rejects (or a composite Q) -- are TFHE_ERR_INVALID_ARGUMENT,
+ * reported before any device call; an N whose BSK row exceeds the LDS (N > 8192) is TFHE_ERR_UNSUPPORTED. */
+
+/* Oracle layouts, device pointers on `device`: d_sk [n] mod qKS, d_bsk_coeff [n][2][dG2][2][N] mod Q (coefficient
+ * form), d_ksk [N][baseKS][dKS][n+1] mod qKS.  d_bsk_coeff / d_ksk may be NULL (that key is skipped); seed_after
+ * may be NULL, else *seed_after = the stream state after the keys.  Runs on `stream` and returns when the keys
+ * are complete. */
+tfhe_status tfhe_keygen_device(const tfhe_params* p, uint64_t seed, int device, uint64_t* d_sk, uint64_t* d_bsk_coeff,
+                               uint64_t* d_ksk, uint64_t* seed_after, void* stream);
+/* The same keys generated straight into a ready context: the rows are written into the key arena in its packed,
+ * NTT-domain form on the first device (no coefficient-form key and no host buffer of the keys' size exists), then
+ * replicated and finished as by tfhe_setup.  The context equals tfhe_setup's on tfhe_keygen_device's keys, its key
+ * image byte for byte.  sk_out: host, n words; seed_after may be NULL. */
+tfhe_status tfhe_setup_keygen(tfhe_ctx** out, const tfhe_params* p, uint64_t seed, int num_gpus, uint64_t* sk_out,
+                              uint64_t* seed_after);
+/* d_m[B] -> d_ct[B][n+1] mod `mod` under d_sk (n words mod qKS); queued on `stream`.  seed_after may be NULL. */
+tfhe_status tfhe_encrypt_device(const tfhe_params* p, int device, const uint64_t* d_sk, size_t B, const int64_t* d_m,
+                                uint64_t ptxt_mod, uint64_t mod, uint64_t seed, uint64_t* d_ct, uint64_t* seed_after,
+                                void* stream);
+/* d_ct[B][n+1] mod `mod` -> d_m[B]; queued on `stream` */
+tfhe_status tfhe_decrypt_device(const tfhe_params* p, int device, const uint64_t* d_sk, size_t B, const uint64_t* d_ct,
+                                uint64_t ptxt_mod, uint64_t mod, int64_t* d_m, void* stream);
+/* The same on host arrays, staged through `device` on `stream`; they return when the output is in host memory. */
+tfhe_status tfhe_encrypt(const tfhe_params* p, int device, const uint64_t* sk, size_t B, const int64_t* m,
+                         uint64_t ptxt_mod, uint64_t mod, uint64_t seed, uint64_t* ct, uint64_t* seed_after,
+                         void* stream);
+tfhe_status tfhe_decrypt(const tfhe_params* p, int device, const uint64_t* sk, size_t B, const uint64_t* ct,
+                         uint64_t ptxt_mod, uint64_t mod, int64_t* m, void* stream);
+
 /* ---- key replication for one-process-per-GPU deployments ----
  * The packed device key image (NTT-domain BSK with Shoup companions, packed
  * KSK, tables) can be copied device-to-device (e.g. broadcast over RCCL/xGMI by

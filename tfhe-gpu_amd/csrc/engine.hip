@@ -346,6 +346,34 @@ void pack_ksk(std::vector<unsigned char>& img, const ArenaLayout& L, uint32_t n,
     });
 }
 
+// The table sections of the key image (psi, ipsi, mono with their companions, eidx: everything below L.bsk)
+// and, when bsk_ntt is given, the NTT-domain BSK with its companions.
+tfhe_status fill_table_image(tfhe_ctx* c, const NttTables& t, const uint64_t* bsk_ntt, std::vector<unsigned char>& img) {
+    const tfhe_params& p = c->p;
+    const ArenaLayout& L = c->layout;
+    auto put = [&](auto tag, size_t off, size_t off_sh, const uint64_t* v, size_t count) {
+        using W = decltype(tag);
+        fill_words<W>(img, off, v, count);
+        if (off_sh != (size_t)-1) fill_companions<W>(img, off_sh, v, count, p.Q);
+    };
+    if (c->word_bits == 32) {
+        put(uint32_t{}, L.psi, L.psi_sh, t.psi_br.data(), p.N);
+        put(uint32_t{}, L.ipsi, L.ipsi_sh, t.ipsi_br.data(), p.N);
+        put(uint32_t{}, L.mono, L.mono_sh, t.mono.data(), 2ull * p.N);
+        if (bsk_ntt) put(uint32_t{}, L.bsk, L.bsk_sh, bsk_ntt, L.bsk_words);
+    } else {
+        put(uint64_t{}, L.psi, L.psi_sh, t.psi_br.data(), p.N);
+        put(uint64_t{}, L.ipsi, L.ipsi_sh, t.ipsi_br.data(), p.N);
+        put(uint64_t{}, L.mono, L.mono_sh, t.mono.data(), 2ull * p.N);
+        if (bsk_ntt) put(uint64_t{}, L.bsk, L.bsk_sh, bsk_ntt, L.bsk_words);
+    }
+    std::memcpy(img.data() + L.eidx, t.eidx.data(), sizeof(uint32_t) * p.N);
+    if (c->use_fast)  // the fast kernel derives e_x = 2 bitrev(x) + 1 in registers
+        for (uint32_t x = 0; x < p.N; ++x)
+            if (t.eidx[x] != 2 * bitrev(x, t.logN) + 1) return fail(TFHE_ERR_INTERNAL, "eidx is not 2 bitrev(x) + 1");
+    return TFHE_OK;
+}
+
 // Build the whole key image on the host (one-time, GPUSetup_core's job in the
 // reference, bootstrapping.cu:874-1083).
 tfhe_status build_host_image(tfhe_ctx* c, const uint64_t* bsk, bool bsk_eval, const uint64_t* ksk,
@@ -357,26 +385,7 @@ tfhe_status build_host_image(tfhe_ctx* c, const uint64_t* bsk, bool bsk_eval, co
     std::vector<uint64_t> bsk_ntt(L.bsk_words);
     if (!bsk_to_ntt_scaled(p, t, bsk, bsk_eval, bsk_ntt.data()))
         return fail(TFHE_ERR_INVALID_ARGUMENT, "evaluation-format BSK entry >= Q");
-    auto put = [&](auto tag, size_t off, size_t off_sh, const uint64_t* v, size_t count) {
-        using W = decltype(tag);
-        fill_words<W>(img, off, v, count);
-        if (off_sh != (size_t)-1) fill_companions<W>(img, off_sh, v, count, p.Q);
-    };
-    if (c->word_bits == 32) {
-        put(uint32_t{}, L.psi, L.psi_sh, t.psi_br.data(), p.N);
-        put(uint32_t{}, L.ipsi, L.ipsi_sh, t.ipsi_br.data(), p.N);
-        put(uint32_t{}, L.mono, L.mono_sh, t.mono.data(), 2ull * p.N);
-        put(uint32_t{}, L.bsk, L.bsk_sh, bsk_ntt.data(), L.bsk_words);
-    } else {
-        put(uint64_t{}, L.psi, L.psi_sh, t.psi_br.data(), p.N);
-        put(uint64_t{}, L.ipsi, L.ipsi_sh, t.ipsi_br.data(), p.N);
-        put(uint64_t{}, L.mono, L.mono_sh, t.mono.data(), 2ull * p.N);
-        put(uint64_t{}, L.bsk, L.bsk_sh, bsk_ntt.data(), L.bsk_words);
-    }
-    std::memcpy(img.data() + L.eidx, t.eidx.data(), sizeof(uint32_t) * p.N);
-    if (c->use_fast)  // the fast kernel derives e_x = 2 bitrev(x) + 1 in registers
-        for (uint32_t x = 0; x < p.N; ++x)
-            if (t.eidx[x] != 2 * bitrev(x, t.logN) + 1) return fail(TFHE_ERR_INTERNAL, "eidx is not 2 bitrev(x) + 1");
+    SCHECK(fill_table_image(c, t, bsk_ntt.data(), img));
     // KSK: packed to the narrowest word holding qKS (reference keeps u64, bootstrapping.cu:963)
     const uint64_t qks = p.qKS;
     std::atomic<bool> bad{false};
@@ -1626,6 +1635,298 @@ tfhe_status tfhe_setup_eval(tfhe_ctx** out, const tfhe_params* p, const uint64_t
                             int num_gpus) {
     return guarded([&]() -> tfhe_status {
         return setup_common(out, p, bsk_eval, true, ksk, num_gpus);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// key generation, encryption, decryption on the device (keygen_kernels.hip)
+// ---------------------------------------------------------------------------
+extern "C++" {
+namespace {
+constexpr uint64_t kGamma = 0x9E3779B97F4A7C15ull;  // splitmix64's increment: draw k reads state + (k + 1) gamma
+
+uint64_t host_draw(uint64_t& state) {
+    uint64_t z = (state += kGamma);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// The finished parameters of a keygen / encrypt / decrypt call (argument errors come before any HIP call).
+tfhe_status finished_params(const tfhe_params* p, tfhe_params& out) {
+    if (!p) return fail(TFHE_ERR_INVALID_ARGUMENT, "null params");
+    out = *p;
+    std::string err;
+    if (params_finish(&out, &err) != TFHE_OK) return fail(TFHE_ERR_INVALID_ARGUMENT, err);
+    return TFHE_OK;
+}
+tfhe_status keygen_params(const tfhe_params* p, tfhe_params& out) {
+    SCHECK(finished_params(p, out));
+    if (!is_prime(out.Q)) return fail(TFHE_ERR_INVALID_ARGUMENT, "Q must be a prime = 1 mod 2N");
+    if (keygen_bsk_lds_bytes(out.N, word_bits_for(out), true) > kKeygenMaxLds)
+        return fail(TFHE_ERR_UNSUPPORTED, "key generation: a BSK row of this N does not fit the LDS");
+    return TFHE_OK;
+}
+
+// Host side of one key generation: s and sN (the stream's first n + N draws), NTT(sN) N^-1, the gadget and
+// key-switching powers, and the stream states in front of the KSK and BSK rows.  blob holds the small arrays the
+// row kernels read (kernels.hpp KeygenTables), uploaded as one buffer; with own_tables it starts with a copy of
+// the NTT tables (tfhe_keygen_device has no arena to take them from).
+struct KeygenHost {
+    KeygenParams kp{};
+    std::vector<uint64_t> sk;  // s mod qKS
+    uint64_t end_state = 0;    // the stream state after the keys
+    std::vector<unsigned char> blob;
+    size_t o_psi = 0, o_psi_sh = 0, o_ipsi = 0, o_ipsi_sh = 0, o_snt = 0, o_snt_sh = 0, o_s = 0, o_sN = 0, o_g = 0,
+           o_gN = 0, o_pw = 0;
+};
+
+void keygen_prepare(const tfhe_params& p, int word_bits, size_t n_pad, uint64_t seed, const NttTables& t,
+                    bool own_tables, KeygenHost& h) {
+    const uint32_t n = p.n, N = p.N, digits = p.dG2 / 2;
+    const size_t wb = word_bits / 8;
+    uint64_t state = seed;
+    std::vector<int8_t> s(n), sN(N);
+    h.sk.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        s[i] = (int8_t)((int)(host_draw(state) % 3) - 1);
+        h.sk[i] = s[i] < 0 ? p.qKS - 1 : (uint64_t)s[i];
+    }
+    for (uint32_t i = 0; i < N; ++i) sN[i] = (int8_t)((int)(host_draw(state) % 3) - 1);
+    KeygenParams& kp = h.kp;
+    kp.N = N, kp.n = n, kp.dG2 = p.dG2, kp.baseKS = p.baseKS, kp.dKS = p.dKS, kp.n_pad = (uint32_t)n_pad;
+    kp.Q = p.Q, kp.qKS = p.qKS;
+    kp.ksk_rows = (size_t)N * p.baseKS * p.dKS;
+    kp.bsk_rows = (size_t)n * 2 * p.dG2;
+    kp.ksk_state = state;
+    kp.bsk_state = kp.ksk_state + (uint64_t)kp.ksk_rows * (n + 2) * kGamma;
+    h.end_state = kp.bsk_state + (uint64_t)kp.bsk_rows * 3 * N * kGamma;
+    kp.Ninv = t.Ninv;
+    kp.Ninv_sh = shoup_companion(t.Ninv, p.Q, word_bits);
+    std::vector<uint64_t> snt(N), g(digits), gN(digits), pw(p.dKS);
+    for (uint32_t x = 0; x < N; ++x) snt[x] = sN[x] < 0 ? p.Q - 1 : (uint64_t)sN[x];
+    host_ntt_fwd(t, snt.data());
+    for (uint32_t x = 0; x < N; ++x) snt[x] = mulmod(snt[x], t.Ninv, p.Q);
+    for (uint32_t d = 0; d < digits; ++d) {
+        g[d] = powmod(p.baseG, d + p.numDigitsToThrow, p.Q);
+        gN[d] = mulmod(g[d], t.Ninv, p.Q);
+    }
+    uint64_t pk = 1 % p.qKS;
+    for (uint32_t k = 0; k < p.dKS; ++k, pk = mulmod(pk, p.baseKS, p.qKS)) pw[k] = pk;
+
+    size_t o = 0;
+    auto take = [&o](size_t bytes) {
+        const size_t at = o;
+        o = align_up(o + bytes);
+        return at;
+    };
+    if (own_tables) h.o_psi = take(N * wb), h.o_psi_sh = take(N * wb), h.o_ipsi = take(N * wb), h.o_ipsi_sh = take(N * wb);
+    h.o_snt = take(N * wb), h.o_snt_sh = take(N * wb);
+    h.o_s = take(n), h.o_sN = take(N);
+    h.o_g = take(digits * 8), h.o_gN = take(digits * 8), h.o_pw = take((size_t)p.dKS * 8);
+    h.blob.assign(o, 0);
+    auto put = [&](size_t off, size_t off_sh, const uint64_t* v) {
+        if (word_bits == 32) fill_words<uint32_t>(h.blob, off, v, N), fill_companions<uint32_t>(h.blob, off_sh, v, N, p.Q);
+        else fill_words<uint64_t>(h.blob, off, v, N), fill_companions<uint64_t>(h.blob, off_sh, v, N, p.Q);
+    };
+    if (own_tables) put(h.o_psi, h.o_psi_sh, t.psi_br.data()), put(h.o_ipsi, h.o_ipsi_sh, t.ipsi_br.data());
+    put(h.o_snt, h.o_snt_sh, snt.data());
+    std::memcpy(h.blob.data() + h.o_s, s.data(), n);
+    std::memcpy(h.blob.data() + h.o_sN, sN.data(), N);
+    std::memcpy(h.blob.data() + h.o_g, g.data(), digits * 8);
+    std::memcpy(h.blob.data() + h.o_gN, gN.data(), digits * 8);
+    std::memcpy(h.blob.data() + h.o_pw, pw.data(), (size_t)p.dKS * 8);
+}
+
+// dev: the uploaded blob; arena: the context's tables, or null to use the blob's own copy
+KeygenTables keygen_tables(const KeygenHost& h, const unsigned char* dev, const DevTables* arena) {
+    KeygenTables T{};
+    T.psi = arena ? arena->psi : dev + h.o_psi;
+    T.psi_sh = arena ? arena->psi_sh : dev + h.o_psi_sh;
+    T.ipsi = arena ? arena->ipsi : dev + h.o_ipsi;
+    T.ipsi_sh = arena ? arena->ipsi_sh : dev + h.o_ipsi_sh;
+    T.snt = dev + h.o_snt;
+    T.snt_sh = dev + h.o_snt_sh;
+    T.s = reinterpret_cast<const int8_t*>(dev + h.o_s);
+    T.sN = reinterpret_cast<const int8_t*>(dev + h.o_sN);
+    T.g = reinterpret_cast<const uint64_t*>(dev + h.o_g);
+    T.gN = reinterpret_cast<const uint64_t*>(dev + h.o_gN);
+    T.pw = reinterpret_cast<const uint64_t*>(dev + h.o_pw);
+    return T;
+}
+
+tfhe_status check_lwe_call(const tfhe_params* p, const void* sk, size_t B, const void* in, const void* out,
+                           uint64_t ptxt_mod, uint64_t mod, tfhe_params& fp) {
+    if (!sk || !in || !out) return fail(TFHE_ERR_INVALID_ARGUMENT, "null argument");
+    SCHECK(finished_params(p, fp));
+    if (B == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "B must be at least 1");
+    if (mod == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "mod must not be 0");
+    if (ptxt_mod == 0 || ptxt_mod > mod) return fail(TFHE_ERR_INVALID_ARGUMENT, "ptxt_mod must be in 1 .. mod");
+    return TFHE_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+tfhe_status tfhe_keygen_device(const tfhe_params* p, uint64_t seed, int device, uint64_t* d_sk, uint64_t* d_bsk_coeff,
+                               uint64_t* d_ksk, uint64_t* seed_after, void* stream) {
+    return guarded([&]() -> tfhe_status {
+        if (!d_sk) return fail(TFHE_ERR_INVALID_ARGUMENT, "null argument");
+        tfhe_params fp;
+        SCHECK(keygen_params(p, fp));
+        const int word_bits = word_bits_for(fp);
+        KeygenHost h;
+        keygen_prepare(fp, word_bits, 0, seed, make_ntt_tables(fp.Q, fp.N), true, h);
+        HCHECK(hipSetDevice(device));
+        hipStream_t s = (hipStream_t)stream;
+        DevBuf blob;
+        HCHECK(hipMalloc(&blob.p, h.blob.size()));
+        HCHECK(hipMemcpyAsync(blob.p, h.blob.data(), h.blob.size(), hipMemcpyHostToDevice, s));
+        HCHECK(hipMemcpyAsync(d_sk, h.sk.data(), sizeof(uint64_t) * fp.n, hipMemcpyHostToDevice, s));
+        const KeygenTables T = keygen_tables(h, blob.as<unsigned char>(), nullptr);
+        if (d_ksk) HCHECK(launch_keygen_ksk(h.kp, T, 0, d_ksk, nullptr, s));
+        if (d_bsk_coeff) HCHECK(launch_keygen_bsk(h.kp, T, word_bits, false, d_bsk_coeff, nullptr, s));
+        HCHECK(hipStreamSynchronize(s));  // the kernels read blob and the copies read h
+        if (seed_after) *seed_after = h.end_state;
+        return TFHE_OK;
+    });
+}
+
+tfhe_status tfhe_setup_keygen(tfhe_ctx** out, const tfhe_params* p, uint64_t seed, int num_gpus, uint64_t* sk_out,
+                              uint64_t* seed_after) {
+    return guarded([&]() -> tfhe_status {
+        if (!out || !sk_out) return fail(TFHE_ERR_INVALID_ARGUMENT, "null argument");
+        *out = nullptr;
+        tfhe_params fp;
+        SCHECK(keygen_params(p, fp));
+        std::unique_ptr<tfhe_ctx> c;
+        SCHECK(create_ctx(p, num_gpus, c));
+        const ArenaLayout& L = c->layout;
+        // host: the table sections (everything below L.bsk) and the small arrays of the row kernels; no buffer
+        // here grows with the keys
+        const NttTables t = make_ntt_tables(fp.Q, fp.N);
+        std::vector<unsigned char> img(L.bsk, 0);
+        SCHECK(fill_table_image(c.get(), t, nullptr, img));
+        KeygenHost h;
+        keygen_prepare(c->p, c->word_bits, L.n_pad, seed, t, false, h);
+        const size_t bytes = L.total;
+        for (size_t g = 0; g < c->devs.size(); ++g) {
+            Device& d = c->devs[g];
+            HCHECK(hipSetDevice(d.id));
+            SCHECK(create_streams(d));
+            HCHECK(hipMalloc(&d.arena, bytes));
+        }
+        Device& d = c->devs[0];
+        HCHECK(hipSetDevice(d.id));
+        {
+            DevBuf blob;
+            HCHECK(hipMalloc(&blob.p, h.blob.size()));
+            // gaps between sections and the pad columns of the KSK are zero, as in build_host_image's image
+            HCHECK(hipMemsetAsync(d.arena, 0, bytes, d.stream));
+            HCHECK(hipMemcpyAsync(d.arena, img.data(), img.size(), hipMemcpyHostToDevice, d.stream));
+            HCHECK(hipMemcpyAsync(blob.p, h.blob.data(), h.blob.size(), hipMemcpyHostToDevice, d.stream));
+            bind_tables(c.get(), d);
+            const KeygenTables T = keygen_tables(h, blob.as<unsigned char>(), &d.tables);
+            hipEvent_t ev[3] = {};  // TFHE_TRACE: the two row kernels' device times (tools/keygen_bench.py)
+            if (c->kn.trace)
+                for (auto& e : ev) HCHECK(hipEventCreate(&e));
+            if (c->kn.trace) HCHECK(hipEventRecord(ev[0], d.stream));
+            HCHECK(launch_keygen_ksk(h.kp, T, c->ksk_bits, d.arena + L.ksk, d.arena + L.kskb, d.stream));
+            if (c->kn.trace) HCHECK(hipEventRecord(ev[1], d.stream));
+            HCHECK(launch_keygen_bsk(h.kp, T, c->word_bits, true, d.arena + L.bsk, d.arena + L.bsk_sh, d.stream));
+            if (c->kn.trace) HCHECK(hipEventRecord(ev[2], d.stream));
+            HCHECK(hipStreamSynchronize(d.stream));
+            if (c->kn.trace) {
+                float ksk_ms = 0, bsk_ms = 0;
+                HCHECK(hipEventElapsedTime(&ksk_ms, ev[0], ev[1]));
+                HCHECK(hipEventElapsedTime(&bsk_ms, ev[1], ev[2]));
+                for (auto& e : ev) hipEventDestroy(e);
+                std::fprintf(stderr, "[tfhe] keygen: ksk %.3f ms, %zu rows, %zu bytes; bsk %.3f ms, %zu rows, %zu bytes\n",
+                             ksk_ms, h.kp.ksk_rows, L.kskb + L.ksk_rows * (c->ksk_bits / 8) - L.ksk, bsk_ms,
+                             h.kp.bsk_rows, 2 * L.bsk_words * (size_t)(c->word_bits / 8));
+            }
+        }
+        SCHECK(replicate_arena(c.get(), bytes));
+        SCHECK(run_shards(
+            c->devs.size(), 2 * c->devs.size(),
+            [&](size_t g) -> tfhe_status {
+                HCHECK(hipSetDevice(c->devs[g].id));
+                return TFHE_OK;
+            },
+            [&](size_t g, size_t, size_t) { return finish_device(c.get(), c->devs[g]); }));
+        std::memcpy(sk_out, h.sk.data(), sizeof(uint64_t) * fp.n);
+        if (seed_after) *seed_after = h.end_state;
+        *out = c.release();
+        return TFHE_OK;
+    });
+}
+
+tfhe_status tfhe_encrypt_device(const tfhe_params* p, int device, const uint64_t* d_sk, size_t B, const int64_t* d_m,
+                                uint64_t ptxt_mod, uint64_t mod, uint64_t seed, uint64_t* d_ct, uint64_t* seed_after,
+                                void* stream) {
+    return guarded([&]() -> tfhe_status {
+        tfhe_params fp;
+        SCHECK(check_lwe_call(p, d_sk, B, d_m, d_ct, ptxt_mod, mod, fp));
+        HCHECK(hipSetDevice(device));
+        HCHECK(launch_lwe_encrypt(fp.n, fp.qKS, d_sk, B, d_m, ptxt_mod, mod, seed, d_ct, (hipStream_t)stream));
+        if (seed_after) *seed_after = seed + (uint64_t)B * (fp.n + 2) * kGamma;
+        return TFHE_OK;
+    });
+}
+
+tfhe_status tfhe_decrypt_device(const tfhe_params* p, int device, const uint64_t* d_sk, size_t B, const uint64_t* d_ct,
+                                uint64_t ptxt_mod, uint64_t mod, int64_t* d_m, void* stream) {
+    return guarded([&]() -> tfhe_status {
+        tfhe_params fp;
+        SCHECK(check_lwe_call(p, d_sk, B, d_ct, d_m, ptxt_mod, mod, fp));
+        HCHECK(hipSetDevice(device));
+        HCHECK(launch_lwe_decrypt(fp.n, fp.qKS, d_sk, B, d_ct, ptxt_mod, mod, d_m, (hipStream_t)stream));
+        return TFHE_OK;
+    });
+}
+
+tfhe_status tfhe_encrypt(const tfhe_params* p, int device, const uint64_t* sk, size_t B, const int64_t* m,
+                         uint64_t ptxt_mod, uint64_t mod, uint64_t seed, uint64_t* ct, uint64_t* seed_after,
+                         void* stream) {
+    return guarded([&]() -> tfhe_status {
+        tfhe_params fp;
+        SCHECK(check_lwe_call(p, sk, B, m, ct, ptxt_mod, mod, fp));
+        HCHECK(hipSetDevice(device));
+        hipStream_t s = (hipStream_t)stream;
+        const size_t skb = sizeof(uint64_t) * fp.n, ctb = sizeof(uint64_t) * B * (fp.n + 1);
+        DevBuf dsk, dm, dct;
+        HCHECK(hipMalloc(&dsk.p, skb));
+        HCHECK(hipMalloc(&dm.p, sizeof(int64_t) * B));
+        HCHECK(hipMalloc(&dct.p, ctb));
+        HCHECK(hipMemcpyAsync(dsk.p, sk, skb, hipMemcpyHostToDevice, s));
+        HCHECK(hipMemcpyAsync(dm.p, m, sizeof(int64_t) * B, hipMemcpyHostToDevice, s));
+        HCHECK(launch_lwe_encrypt(fp.n, fp.qKS, dsk.as<uint64_t>(), B, dm.as<int64_t>(), ptxt_mod, mod, seed,
+                                  dct.as<uint64_t>(), s));
+        HCHECK(hipMemcpyAsync(ct, dct.p, ctb, hipMemcpyDeviceToHost, s));
+        HCHECK(hipStreamSynchronize(s));
+        if (seed_after) *seed_after = seed + (uint64_t)B * (fp.n + 2) * kGamma;
+        return TFHE_OK;
+    });
+}
+
+tfhe_status tfhe_decrypt(const tfhe_params* p, int device, const uint64_t* sk, size_t B, const uint64_t* ct,
+                         uint64_t ptxt_mod, uint64_t mod, int64_t* m, void* stream) {
+    return guarded([&]() -> tfhe_status {
+        tfhe_params fp;
+        SCHECK(check_lwe_call(p, sk, B, ct, m, ptxt_mod, mod, fp));
+        HCHECK(hipSetDevice(device));
+        hipStream_t s = (hipStream_t)stream;
+        const size_t skb = sizeof(uint64_t) * fp.n, ctb = sizeof(uint64_t) * B * (fp.n + 1);
+        DevBuf dsk, dm, dct;
+        HCHECK(hipMalloc(&dsk.p, skb));
+        HCHECK(hipMalloc(&dm.p, sizeof(int64_t) * B));
+        HCHECK(hipMalloc(&dct.p, ctb));
+        HCHECK(hipMemcpyAsync(dsk.p, sk, skb, hipMemcpyHostToDevice, s));
+        HCHECK(hipMemcpyAsync(dct.p, ct, ctb, hipMemcpyHostToDevice, s));
+        HCHECK(launch_lwe_decrypt(fp.n, fp.qKS, dsk.as<uint64_t>(), B, dct.as<uint64_t>(), ptxt_mod, mod,
+                                  dm.as<int64_t>(), s));
+        HCHECK(hipMemcpyAsync(m, dm.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, s));
+        HCHECK(hipStreamSynchronize(s));
+        return TFHE_OK;
     });
 }
 

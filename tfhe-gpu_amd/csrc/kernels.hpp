@@ -239,6 +239,43 @@ hipError_t launch_lwe_op(uint32_t op, uint32_t n, uint64_t m, uint64_t c, const 
 constexpr unsigned kChecksumBlocks = 1024;
 hipError_t launch_checksum(const void* p, size_t bytes, uint64_t* partial, hipStream_t s);
 
+// ---- key generation, encryption, decryption (keygen_kernels.hip; the stream: include/tfhe_hip.h) ----
+// *_state: the splitmix64 state in front of the first KSK / BSK row's first draw.
+struct KeygenParams {
+    uint32_t N, n, dG2, baseKS, dKS, n_pad;
+    uint64_t Q, qKS;
+    uint64_t ksk_state, bsk_state;
+    uint64_t Ninv, Ninv_sh;  // N^-1 mod Q and its Shoup companion at the context's word width
+    size_t ksk_rows, bsk_rows;
+};
+// Small device arrays of one key generation (engine.hip keygen_prepare).  W = the context's word class.
+struct KeygenTables {
+    const void *psi, *psi_sh, *ipsi, *ipsi_sh;  // [N] of W: the context's NTT tables
+    const void *snt, *snt_sh;                   // [N] of W: NTT(sN) N^-1 and its Shoup companions
+    const int8_t* s;                            // [n] LWE key, ternary
+    const int8_t* sN;                           // [N] ring key, ternary
+    const uint64_t* g;                          // [dG2 / 2] baseG^(d + numDigitsToThrow) mod Q
+    const uint64_t* gN;                         // [dG2 / 2] the same times N^-1
+    const uint64_t* pw;                         // [dKS] baseKS^k mod qKS
+};
+constexpr size_t kKeygenMaxLds = 160 * 1024;
+size_t keygen_bsk_lds_bytes(uint32_t N, int word_bits, bool arena);
+// ksk_bits 0: out_a is the caller's [rows][n+1] u64 array (out_b unused); 16 / 32 / 64: the arena's packed A
+// part [rows][n_pad] and B part [rows] at that width (pad columns are written as zeros)
+hipError_t launch_keygen_ksk(const KeygenParams& P, const KeygenTables& T, int ksk_bits, void* out_a, void* out_b,
+                             hipStream_t s);
+// arena: out / out_sh = the arena's bsk / bsk_sh regions (NTT domain, scaled by N^-1, and Shoup companions) in
+// word_bits words; else out = the caller's coefficient-form [rows][2][N] u64 array (out_sh unused).
+// hipErrorNotSupported when the row does not fit the LDS (keygen_bsk_lds_bytes > kKeygenMaxLds).
+hipError_t launch_keygen_bsk(const KeygenParams& P, const KeygenTables& T, int word_bits, bool arena, void* out,
+                             void* out_sh, hipStream_t s);
+// or_encrypt / or_decrypt on B ciphertexts [B][n+1] mod `mod`; sk mod qKS; ciphertext b draws from
+// seed + b (n + 2) positions
+hipError_t launch_lwe_encrypt(uint32_t n, uint64_t qKS, const uint64_t* sk, size_t B, const int64_t* msg,
+                              uint64_t ptxt_mod, uint64_t mod, uint64_t seed, uint64_t* ct, hipStream_t s);
+hipError_t launch_lwe_decrypt(uint32_t n, uint64_t qKS, const uint64_t* sk, size_t B, const uint64_t* ct,
+                              uint64_t ptxt_mod, uint64_t mod, int64_t* msg, hipStream_t s);
+
 // CiphertextMulMatrix: out[c][w] = sum_k matrix[k][c] * ct[k][w] mod modulus.
 // ct and matrix are device copies the launch reduces in place into [0, modulus).
 hipError_t launch_ct_mul_matrix(uint32_t width, size_t K, uint64_t* ct, size_t cols, int64_t* matrix,

@@ -7,14 +7,16 @@ and mirrors the vector ``BinFHEContext`` surface of the reference
 ``EvalFloor``, ``EvalSign``, ``EvalDecomp``, plus the low-level
 ``EvalAcc``/``MKMSwitch`` boundary calls, ``Circuit`` / ``EvalCircuit``:
 a netlist of mixed gates evaluated level by level on the device, and ``FuncCircuit`` / ``EvalFuncCircuit``: the
-same for netlists of linear forms and LUT bootstraps over Z_q.  There is no CPU fallback: if the
+same for netlists of linear forms and LUT bootstraps over Z_q.  ``BinFHEContextHIP.from_keygen``, ``Encrypt``,
+``Decrypt`` and ``keygen`` generate keys and ciphertexts on the device from a seeded splitmix64 stream (tests,
+benchmarks, reproducible experiments -- not a cryptographic generator).  There is no CPU fallback: if the
 library or a GPU is missing, calls raise.
 """
 from .capi import (BINGATE, CIRCUIT_OPS, FCIRCUIT_OPS, PARAMSETS, TfheError, Params, lib, library_path, build, exported_symbols,
                    params_from_set, params_from_logq, host_selftest)
 from .circuit import Circuit
 from .fcircuit import FuncCircuit
-from .context import BinFHEContextHIP
+from .context import BinFHEContextHIP, keygen
 
 __all__ = ["BINGATE", "CIRCUIT_OPS", "Circuit", "FCIRCUIT_OPS", "FuncCircuit", "PARAMSETS", "TfheError", "Params", "lib", "library_path", "build", "exported_symbols",
-           "params_from_set", "params_from_logq", "host_selftest", "BinFHEContextHIP"]
+           "params_from_set", "params_from_logq", "host_selftest", "BinFHEContextHIP", "keygen"]

@@ -144,6 +144,12 @@ _SIGS = {
     "tfhe_fcircuit_eval_plain": ([VP, SZ, VP, VP], C.c_int),
     "tfhe_eval_fcircuit_device": ([VP, VP, SZ, VP, VP, VP], C.c_int),
     "tfhe_eval_fcircuit": ([VP, VP, SZ, u64p, u64p], C.c_int),
+    "tfhe_keygen_device": ([P, U64, C.c_int, VP, VP, VP, C.POINTER(U64), VP], C.c_int),
+    "tfhe_setup_keygen": ([C.POINTER(VP), P, U64, C.c_int, u64p, C.POINTER(U64)], C.c_int),
+    "tfhe_encrypt_device": ([P, C.c_int, VP, SZ, VP, U64, U64, U64, VP, C.POINTER(U64), VP], C.c_int),
+    "tfhe_decrypt_device": ([P, C.c_int, VP, SZ, VP, U64, U64, VP, VP], C.c_int),
+    "tfhe_encrypt": ([P, C.c_int, u64p, SZ, i64p, U64, U64, U64, u64p, C.POINTER(U64), VP], C.c_int),
+    "tfhe_decrypt": ([P, C.c_int, u64p, SZ, u64p, U64, U64, i64p, VP], C.c_int),
     "tfhe_export_key_image": ([VP, VP, SZ, VP], C.c_int),
     "tfhe_setup_from_key_image": ([C.POINTER(VP), P, VP, SZ, C.c_int], C.c_int),
     "tfhe_save_key_image": ([VP, C.c_char_p], C.c_int),

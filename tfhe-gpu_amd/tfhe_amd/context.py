@@ -12,6 +12,9 @@ import numpy as np
 from .capi import BINGATE, Info, Knobs, Params, check, lib
 
 
+_M64 = (1 << 64) - 1
+
+
 def _u64(x):
     return np.ascontiguousarray(x, dtype=np.uint64)
 
@@ -25,6 +28,35 @@ def _rows(x, width: int, what: str):
     if x.ndim != 2 or x.shape[1] != width:
         raise ValueError(f"{what}: expected shape (B, {width}), got {x.shape}")
     return x
+
+
+def keygen(params: Params, seed: int, device: int = 0, want_bsk: bool = True, want_ksk: bool = True):
+    """(sk, bsk_coeff, ksk): the keys of stream `seed` in the oracle's layouts (include/tfhe_hip.h), generated on
+    `device` (tfhe_keygen_device) and copied to numpy arrays; a key that is not wanted is None.  keygen.seed_after
+    holds the stream state behind the last call."""
+    import torch
+
+    dev = torch.device("cuda", device)
+
+    def buf(words):
+        return torch.empty(words, dtype=torch.int64, device=dev)
+
+    d_sk = buf(params.n)
+    d_bsk = buf(params.bsk_words()) if want_bsk else None
+    d_ksk = buf(params.ksk_words()) if want_ksk else None
+    after = C.c_uint64()
+    torch.cuda.synchronize(dev)
+    L = lib()
+    check(L.tfhe_keygen_device(C.byref(params), seed & _M64, device, C.c_void_p(d_sk.data_ptr()),
+                               C.c_void_p(d_bsk.data_ptr() if want_bsk else None),
+                               C.c_void_p(d_ksk.data_ptr() if want_ksk else None), C.byref(after), None),
+          "tfhe_keygen_device", L)
+    keygen.seed_after = after.value
+
+    def host(t):
+        return None if t is None else t.cpu().numpy().view(np.uint64)
+
+    return host(d_sk), host(d_bsk), host(d_ksk)
 
 
 class BinFHEContextHIP:
@@ -70,6 +102,65 @@ class BinFHEContextHIP:
         ctx._check(ctx._L.tfhe_setup_from_key_file(C.byref(ctx._h), C.byref(params), os.fsencode(path), device),
                    "tfhe_setup_from_key_file")
         return ctx
+
+    @classmethod
+    def from_keygen(cls, params: Params, seed: int, num_gpus: int = 1, library: str | None = None):
+        """KeyGen + BTKeyGen on the device (tfhe_setup_keygen): the keys of stream `seed` are generated straight
+        into the context's key arena.  Returns (context, sk); sk: n words mod qKS.  The stream is splitmix64
+        (include/tfhe_hip.h): for tests, benchmarks and reproducible experiments, not a cryptographic generator."""
+        ctx = cls(params, library)
+        sk = np.empty(params.n, dtype=np.uint64)
+        after = C.c_uint64()
+        ctx._check(ctx._L.tfhe_setup_keygen(C.byref(ctx._h), C.byref(params), seed & _M64, num_gpus, sk,
+                                            C.byref(after)), "tfhe_setup_keygen")
+        ctx.seed_after = after.value
+        return ctx, sk
+
+    # -- Encrypt / Decrypt (binfhecontext.cpp:230-252) on the device; host arrays staged through `device` --
+    def Encrypt(self, sk, m, p: int = 4, mod: int | None = None, seed: int = 0, device: int = 0):
+        """m: B messages (negative and >= p are reduced mod p) -> ciphertexts [B, n+1] mod `mod` (default q).
+        Ciphertext b reads the stream from seed + b (n + 2) draws; self.seed_after is the state behind the call."""
+        msg = np.ascontiguousarray(np.atleast_1d(m), dtype=np.int64)
+        if msg.ndim != 1 or msg.size == 0:
+            raise ValueError(f"Encrypt: expected B >= 1 messages, got shape {msg.shape}")
+        sk = self._sk(sk)
+        ct = np.empty((msg.size, self.params.n + 1), dtype=np.uint64)
+        after = C.c_uint64()
+        self._check(self._L.tfhe_encrypt(C.byref(self.params), device, sk, msg.size, msg, p, mod or self.params.q,
+                                         seed & _M64, ct.ravel(), C.byref(after), None), "tfhe_encrypt")
+        self.seed_after = after.value
+        return ct
+
+    def Decrypt(self, sk, ct, p: int = 4, mod: int | None = None, device: int = 0):
+        """ct [B, n+1] mod `mod` (default q) -> the B messages (a list of ints)."""
+        ct, B = self._batch(ct, "Decrypt")
+        if B == 0:
+            raise ValueError("Decrypt: expected B >= 1 ciphertexts")
+        out = np.empty(B, dtype=np.int64)
+        self._check(self._L.tfhe_decrypt(C.byref(self.params), device, self._sk(sk), B, ct.ravel(), p,
+                                         mod or self.params.q, out, None), "tfhe_decrypt")
+        return [int(v) for v in out]
+
+    def _sk(self, sk):
+        sk = _u64(sk).ravel()
+        if sk.size != self.params.n:
+            raise ValueError(f"secret key: expected n = {self.params.n} words, got {sk.size}")
+        return sk
+
+    def EncryptDevice(self, B, d_sk, d_m, d_ct, p: int = 4, mod: int | None = None, seed: int = 0, device: int = 0,
+                      stream=0):
+        """d_sk[n] u64, d_m[B] i64 -> d_ct[B][n+1], device pointers; returns the stream state behind the call."""
+        after = C.c_uint64()
+        self._check(self._L.tfhe_encrypt_device(C.byref(self.params), device, C.c_void_p(d_sk), B, C.c_void_p(d_m), p,
+                                                mod or self.params.q, seed & _M64, C.c_void_p(d_ct), C.byref(after),
+                                                C.c_void_p(stream)), "tfhe_encrypt_device")
+        return after.value
+
+    def DecryptDevice(self, B, d_sk, d_ct, d_m, p: int = 4, mod: int | None = None, device: int = 0, stream=0):
+        """d_ct[B][n+1] -> d_m[B] i64, device pointers."""
+        self._check(self._L.tfhe_decrypt_device(C.byref(self.params), device, C.c_void_p(d_sk), B, C.c_void_p(d_ct), p,
+                                                mod or self.params.q, C.c_void_p(d_m), C.c_void_p(stream)),
+                    "tfhe_decrypt_device")
 
     def save_key_image(self, path: str):
         self._check(self._L.tfhe_save_key_image(self._h, os.fsencode(path)), "tfhe_save_key_image")
