@@ -225,3 +225,23 @@ def test_product_library_has_no_duo_probe(capi, kernel, product, probes):
 
     assert duo(capi.library_path()) == product
     assert duo(capi.capi.TEST_LIB) == probes
+
+
+def test_arithmetic_probes_exist_in_the_test_library_only(capi):
+    """The arithmetic probes (csrc/arith_probes.hpp; tests/test_gpu_arith_units.py) -- one tfhe_test_arith_<family>
+    entry point and one k_arith_<family> kernel per family -- are in lib/libtfhe_hip_test.so and not in the
+    product library, and include/tfhe_hip.h does not declare them."""
+    import re
+    import subprocess
+
+    families = {"dm", "kg", "g3", "sf", "f64", "fast4"}
+
+    def names(path):
+        dyn = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        sym = subprocess.run(["nm", "-C", path], capture_output=True, text=True, check=True).stdout
+        return set(re.findall(r"\btfhe_test_arith_(\w+)", dyn)), set(re.findall(r"\bk_arith_([a-z0-9]+)\b", sym))
+
+    entry, kern = names(capi.capi.TEST_LIB)
+    assert entry == families and kern >= families, (entry, kern)
+    assert names(capi.library_path()) == (set(), set())
+    assert not [s for s in capi.exported_symbols() if s.startswith("tfhe_test_")]

@@ -602,8 +602,9 @@ def _prime_1_mod(m, bits):
 
 @pytest.mark.parametrize("bits,baseG_log", [(35, 12), (45, 15)])
 def test_custom_modulus_n1024_f64_parity(capi, oracle, bits, baseG_log):
-    """User-defined parameters (C-ABI tfhe_params_finish) with a 35-bit / 45-bit Q at N=1024
-    exercise the exact-FP64 kernel's N=1024 instances (plain and reducing)."""
+    """User-defined parameters (C-ABI tfhe_params_finish) with a 35-bit / 45-bit Q at N=1024 run the
+    generic u64 kernel (br_kernel 0): the exact-FP64 kernel's N=1024 instances were removed in round 4
+    (f64_path_supported requires N = 2048; tests/test_gpu_modulus_edges.py runs custom moduli on it)."""
     import ctypes as C
 
     from tfhe_amd import capi as raw
@@ -621,6 +622,7 @@ def test_custom_modulus_n1024_f64_parity(capi, oracle, bits, baseG_log):
     bsk = rs.integers(0, op.Q, cp.bsk_words(), dtype=np.uint64)
     ksk = rs.integers(0, op.qKS, cp.ksk_words(), dtype=np.uint64)
     ctx, orc = make_pair(capi, oracle, op, cp, bsk, ksk)
+    assert ctx.info().br_kernel == 0
     B = 3
     a = rs.integers(0, op.q, (B, op.n), dtype=np.uint64)
     acc = rs.integers(0, op.Q, (B, 2, op.N), dtype=np.uint64)

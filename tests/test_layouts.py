@@ -52,9 +52,17 @@ def test_wave_local_transform_schedule():
 def test_fp64_kernel_bounds():
     """f64w for Q near 2^50 (STD128Q): every sum and fmodmul operand of the forward transform
     (one reduction), products, monomial factors, inverse (passes C and B reduce every output) and
-    accumulator update stays below 2^53 in the worst case; the round-2 inverse schedule did not."""
+    accumulator update stays below 2^53 in the worst case; the round-2 inverse schedule did not.
+    The non-reducing schedule (RED = false, <false, false, 2>) is walked at the largest admitted
+    Q below 2^40: its unreduced inverse sums reach about 2^10 Q = 2^50, and every fmodmul product
+    stays below 2^102."""
     out = run_tool("bounds_f64.py")
     assert out.strip().endswith("OK"), out
+    plain = re.search(r"RED = false at the largest Q < 2\^40: Q = 2\^40\.0+,.*\n.*inverse outputs <= ([0-9.]+) Q\n"
+                      r"\s+largest operand or sum: [0-9.]+ Q = 2\^([0-9.]+) .*OK\n\s+largest fmodmul product: "
+                      r"2\^([0-9.]+)\s+OK", out)
+    assert plain, out
+    assert float(plain.group(1)) == 1024.0 and float(plain.group(2)) < 53 and float(plain.group(3)) < 102, out
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bounds_f64.py"), "--round2"],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 1 and "OVER 2^53" in r.stdout, r.stdout

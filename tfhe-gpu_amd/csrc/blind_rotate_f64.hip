@@ -1074,6 +1074,21 @@ hipError_t launch_pack_bsk_f64(const BRParams& P, const DevTables& T, const void
     return hipGetLastError();
 }
 
+namespace {
+// the kernels' constants (the launcher's and the test library's arithmetic probes'); P: Q, N, logG, digits
+F64Const make_f64_const(const BRParams& P) {
+    F64Const K;
+    K.Q = (double)P.Q;
+    K.Qinv = 1.0 / K.Q;
+    K.Qi = (int64_t)P.Q;
+    const uint64_t ninv = P.Q - (P.Q - 1) / P.N;  // N (Q-1)/N = -1 mod Q
+    K.Ninv = -(double)((P.Q - 1) / P.N);
+    const uint64_t wf = (uint64_t)((unsigned __int128)pow_mod(2, (uint64_t)P.logG * P.digits, P.Q) * ninv % P.Q);
+    K.wfac = wf > P.Q / 2 ? -(double)(P.Q - wf) : (double)wf;
+    return K;
+}
+}  // namespace
+
 bool f64_duo_form(const BRParams& P, bool fold) {
     if (!f64_path_supported(P, 64) || !fold) return false;
     return (P.Q >= (1ull << 40) && !fold_exact(P) && P.digits == 2) ||  // STD128Q class: <RED, WRAP, 1>
@@ -1085,14 +1100,7 @@ hipError_t launch_blind_rotate_f64(const BRParams& P, const DevTables& T, const 
                                    const Knobs& kn, DuoDev* duo) {
     if (B == 0) return hipSuccess;
     if (P.N != 2048 || !f64_instance_available(P, fold)) return hipErrorInvalidValue;
-    F64Const K;
-    K.Q = (double)P.Q;
-    K.Qinv = 1.0 / K.Q;
-    K.Qi = (int64_t)P.Q;
-    const uint64_t ninv = P.Q - (P.Q - 1) / P.N;  // N (Q-1)/N = -1 mod Q
-    K.Ninv = -(double)((P.Q - 1) / P.N);
-    const uint64_t wf = (uint64_t)((unsigned __int128)pow_mod(2, (uint64_t)P.logG * P.digits, P.Q) * ninv % P.Q);
-    K.wfac = wf > P.Q / 2 ? -(double)(P.Q - wf) : (double)wf;
+    const F64Const K = make_f64_const(P);
     const bool wrap = fold && !fold_exact(P);
     // psi, ipsi, two polynomials, monomial tables, rotation exponents
     const size_t lds = ((size_t)4 * P.N + 128) * sizeof(double) + rot_exponent_bytes(P.n);
@@ -1155,3 +1163,58 @@ hipError_t launch_blind_rotate_f64(const BRParams& P, const DevTables& T, const 
 }
 
 }  // namespace tfhe
+
+#ifdef TFHE_TEST_PROBES
+// ---- arithmetic probes (test library only; arith_probes.hpp, tests/test_gpu_arith_units.py) ----
+// op: 0 fmodmul(a, b)  1 fred(x)  2 ct_bf(a, b, w)  3 gs_bf(a, b, w)  4 f64_r8_fwd_core(v[8], m0, g)
+//     5 f64_r8_inv_core(v[8], m, g)
+// 10 words in, 8 out per case (doubles as their bit patterns; m0 / m, g as integers); tab = the twiddle table
+#include "arith_probes.hpp"
+
+namespace tfhe {
+namespace {
+constexpr int F64P_NI = 10, F64P_NO = 8;
+__global__ void k_arith_f64(int op, size_t cases, const uint64_t* __restrict__ in, const uint64_t* __restrict__ tab,
+                            size_t tab_words, uint64_t* __restrict__ out, F64Const K) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!probe_lane_runs(op, i, cases)) return;
+    const double* x = reinterpret_cast<const double*>(in) + i * F64P_NI;
+    double* o = reinterpret_cast<double*>(out) + i * F64P_NO;
+    const double* tw = reinterpret_cast<const double*>(tab);
+    const size_t T = tab_words;
+    const int f = op & 15;
+    if (f == 0) o[0] = fmodmul(x[0], x[1], K);
+    else if (f == 1) o[0] = fred(x[0], K);
+    else if (f == 2 || f == 3) {
+        double a = x[0], b = x[1];
+        if (f == 2) ct_bf(a, b, x[2], K);
+        else gs_bf(a, b, x[2], K);
+        o[0] = a, o[1] = b;
+    } else if (f == 4 || f == 5) {
+        double v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = x[k];
+        const uint64_t m = in[i * F64P_NI + 8], g = in[i * F64P_NI + 9];
+        if (m >= T || g >= T) return;
+        if (f == 4) {
+            if (4 * m + 4 * g + 3 >= T) return;
+            f64_r8_fwd_core(v, (uint32_t)m, (uint32_t)g, tw, K);
+        } else {
+            if ((m & 3) || m + 4 * g + 3 >= T) return;  // (16-byte twiddle pairs)
+            f64_r8_inv_core(v, (uint32_t)m, (uint32_t)g, tw, K);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = v[k];
+    }
+}
+}  // namespace
+}  // namespace tfhe
+
+extern "C" TFHE_ARITH_PROBE(f64) {
+    if ((op & 15) > 5 || Q < (1ull << 32) || Q >= (1ull << 50) || Q % 4096 != 1) return -1;
+    tfhe::BRParams P{};
+    P.Q = Q, P.N = 2048, P.logN = 11, P.logG = 14, P.digits = 3;  // (Ninv and wfac are not the probed functions')
+    return tfhe::probe_launch(tfhe::k_arith_f64, tfhe::F64P_NI, tfhe::F64P_NO, op, cases, in, in_words, tab, tab_words,
+                              out, out_words, tfhe::make_f64_const(P));
+}
+#endif  // TFHE_TEST_PROBES

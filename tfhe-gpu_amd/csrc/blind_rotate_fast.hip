@@ -146,7 +146,16 @@ hipError_t launch_blind_rotate_fast(const BRParams& P, const DevTables&, const v
     if (amod == 0 || (amod & (amod - 1)) || amod > 2 * FN) return hipErrorNotSupported;
     uint32_t loga = 0;
     while ((1ull << loga) < amod) ++loga;
-    const uint32_t Q = (uint32_t)P.Q;
+    FastConst K;
+    fast_const_build((uint32_t)P.Q, &K);
+    const int32_t* tabs = (const int32_t*)bsk_fast;
+    return launch_blind_rotate_fast4(fast_variant(), fast_shape(P), &K, P.n, loga, tabs, tabs + TB_WORDS, a, acc, B, s,
+                                     dn, split_max);
+}
+
+// The kernels' constants for modulus Q (out: a FastConst); shared by the launcher above and the test library's
+// arithmetic probes (blind_rotate_fast4.hip), so the probes run on the real constants.
+void fast_const_build(uint32_t Q, void* out) {
     uint32_t inv = 1;  // Q^-1 mod 2^32 by Newton iteration
     for (int it = 0; it < 5; ++it) inv *= 2u - Q * inv;
     FastConst K;
@@ -161,9 +170,7 @@ hipError_t launch_blind_rotate_fast(const BRParams& P, const DevTables&, const v
     K.kacc = K.h1 + 4 * Q;
     K.ninv = mont_centred(Q - (Q - 1) / FN, Q);  // N (Q-1)/N = -1 mod Q
     K.bm = (uint32_t)((1ull << 32) / Q);
-    const int32_t* tabs = (const int32_t*)bsk_fast;
-    return launch_blind_rotate_fast4(fast_variant(), fast_shape(P), &K, P.n, loga, tabs, tabs + TB_WORDS, a, acc, B, s,
-                                     dn, split_max);
+    *static_cast<FastConst*>(out) = K;
 }
 
 }  // namespace tfhe

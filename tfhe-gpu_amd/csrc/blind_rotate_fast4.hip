@@ -782,3 +782,51 @@ hipError_t launch_blind_rotate_fast4(int variant, const Fast4Shape& sh, const vo
 
 #endif  // TFHE_FAST4_KERNEL_ONLY
 }  // namespace tfhe
+
+#if defined(TFHE_TEST_PROBES) && !defined(TFHE_FAST4_KERNEL_ONLY)
+// ---- arithmetic probes (test library only; arith_probes.hpp, tests/test_gpu_arith_units.py) ----
+// op: 0 sredc(T)  1 smul(a, w)  2 csub32(a, m)  3 bfly_ct(a, b, w)  4 / 5 bfly_gs<RED = 0 / 1>(a, b, w)
+//     6 fwd4(x[4], w1, w2, w3)  7 / 8 inv4<RED = 0 / 1>(x[4], w1, w2, w3)
+// 8 words in, 4 out per case (int32 values sign-extended to 64 bits, T as an int64); no table
+#include "arith_probes.hpp"
+
+namespace tfhe {
+namespace f4 {
+constexpr int F4P_NI = 8, F4P_NO = 4;
+__global__ void k_arith_fast4(int op, size_t cases, const uint64_t* __restrict__ in, const uint64_t* __restrict__,
+                              size_t, uint64_t* __restrict__ out, FastConst K) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!probe_lane_runs(op, i, cases)) return;
+    const int64_t* x = reinterpret_cast<const int64_t*>(in) + i * F4P_NI;
+    int64_t* o = reinterpret_cast<int64_t*>(out) + i * F4P_NO;
+    const int f = op & 15;
+    if (f == 0) o[0] = sredc(x[0], K);
+    else if (f == 1) o[0] = smul((int32_t)x[0], (int32_t)x[1], K);
+    else if (f == 2) o[0] = (int64_t)(uint64_t)csub32((uint32_t)x[0], (uint32_t)x[1]);
+    else if (f >= 3 && f <= 5) {
+        int32_t a = (int32_t)x[0], b = (int32_t)x[1];
+        if (f == 3) bfly_ct(a, b, (int32_t)x[2], K);
+        else if (f == 4) bfly_gs<false>(a, b, (int32_t)x[2], K);
+        else bfly_gs<true>(a, b, (int32_t)x[2], K);
+        o[0] = a, o[1] = b;
+    } else if (f >= 6 && f <= 8) {
+        int32_t v[4] = {(int32_t)x[0], (int32_t)x[1], (int32_t)x[2], (int32_t)x[3]};
+        const int32_t w1 = (int32_t)x[4], w2 = (int32_t)x[5], w3 = (int32_t)x[6];
+        if (f == 6) fwd4(v, w1, w2, w3, K);
+        else if (f == 7) inv4<false>(v, w1, w2, w3, K);
+        else inv4<true>(v, w1, w2, w3, K);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = v[k];
+    }
+}
+}  // namespace f4
+}  // namespace tfhe
+
+extern "C" TFHE_ARITH_PROBE(fast4) {
+    if ((op & 15) > 8 || Q < 3 || Q >= (1ull << 27) || !(Q & 1)) return -1;
+    tfhe::f4::FastConst K;
+    tfhe::fast_const_build((uint32_t)Q, &K);
+    return tfhe::probe_launch(tfhe::f4::k_arith_fast4, tfhe::f4::F4P_NI, tfhe::f4::F4P_NO, op, cases, in, in_words, tab,
+                              tab_words, out, out_words, K);
+}
+#endif  // TFHE_TEST_PROBES

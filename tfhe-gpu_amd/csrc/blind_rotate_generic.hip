@@ -696,3 +696,73 @@ hipError_t launch_blind_rotate_generic(int word_bits, const BRParams& P, const D
 }
 
 }  // namespace tfhe
+
+#ifdef TFHE_TEST_PROBES
+// ---- arithmetic probes (test library only; arith_probes.hpp, tests/test_gpu_arith_units.py) ----
+// op (| 16: the u32 instance): 0 ct_lazy(x, y, w, ws)  1 gs_lazy(x, y, w, ws)  2 g3_fwd_core(v[8], m0, g)
+//     3 g3_inv_core(v[8], m, g)
+// 10 words in, 8 out per case; tab = w[T] then the Shoup companions s[T] (u64 words, truncated for u32)
+#include "arith_probes.hpp"
+
+namespace tfhe {
+namespace {
+constexpr int G3P_NI = 10, G3P_NO = 8, G3P_TAB = 1 << 16;  // (most table pairs an entry takes)
+template <typename W>
+__global__ void k_arith_g3(int op, size_t cases, const uint64_t* __restrict__ in, const uint64_t* __restrict__ tab,
+                           size_t tab_words, uint64_t* __restrict__ out, uint64_t Q64, const W* __restrict__ tw) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!probe_lane_runs(op, i, cases)) return;
+    const uint64_t* x = in + i * G3P_NI;
+    uint64_t* o = out + i * G3P_NO;
+    const W Q = (W)Q64, Q2 = 2 * Q;
+    const size_t T = tab_words / 2;
+    const G3Tw<W> G{tw, tw + T};
+    const int f = op & 15;
+    if (f == 0 || f == 1) {
+        W a = (W)x[0], b = (W)x[1];
+        if (f == 0) ct_lazy<W>(a, b, (W)x[2], (W)x[3], Q2, Q);
+        else gs_lazy<W>(a, b, (W)x[2], (W)x[3], Q2, Q);
+        o[0] = a, o[1] = b;
+    } else {
+        W v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = (W)x[k];
+        const uint64_t m = x[8], g = x[9];
+        if (m >= T || g >= T) return;
+        if (f == 2) {
+            if (4 * m + 4 * g + 3 >= T) return;
+            g3_fwd_core<W>(v, (uint32_t)m, (uint32_t)g, G, Q2, Q);
+        } else {
+            if (m + 4 * g + 3 >= T) return;
+            g3_inv_core<W>(v, (uint32_t)m, (uint32_t)g, G, Q2, Q);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = v[k];
+    }
+}
+// the u32 instance reads a u32 table: the u64 table narrowed on the device
+__global__ void k_arith_g3_narrow(const uint64_t* __restrict__ src, size_t words, uint32_t* __restrict__ dst) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < words) dst[i] = (uint32_t)src[i];
+}
+}  // namespace
+}  // namespace tfhe
+
+extern "C" TFHE_ARITH_PROBE(g3) {
+    using namespace tfhe;
+    const bool u32 = (op >> 4) & 1;
+    if ((op & 15) > 3 || Q < 3 || (tab_words & 1) || tab_words > 2 * (size_t)G3P_TAB) return -1;
+    if (u32 ? Q >= (1ull << 30) : Q >= (1ull << 58)) return -1;  // 4Q fits the word
+    if (!u32)
+        return probe_launch(k_arith_g3<uint64_t>, G3P_NI, G3P_NO, op, cases, in, in_words, tab, tab_words, out, out_words, Q,
+                            tab);
+    uint32_t* narrow = nullptr;
+    if (hipError_t e = hipMalloc(&narrow, (tab_words + 1) * sizeof(uint32_t)); e != hipSuccess) return (int)e;
+    if (tab_words)
+        hipLaunchKernelGGL(k_arith_g3_narrow, dim3((unsigned)((tab_words + 255) / 256)), dim3(256), 0, 0, tab, tab_words, narrow);
+    const int rc = probe_launch(k_arith_g3<uint32_t>, G3P_NI, G3P_NO, op, cases, in, in_words, tab, tab_words, out, out_words,
+                                Q, (const uint32_t*)narrow);
+    (void)hipFree(narrow);
+    return rc;
+}
+#endif  // TFHE_TEST_PROBES

@@ -1363,15 +1363,23 @@ hipError_t launch_pack_sf(const BRParams& P, const DevTables& T, const void* bsk
 
 static_assert(G3_N == kDuoN, "the duo buffer holds N = 2048 polynomials");
 
+namespace {
+// the kernels' constants for Q = 2^54 - c (the launcher's and the test library's arithmetic probes')
+SfC make_sf_const(uint64_t Q) {
+    SfC K;
+    K.Q = Q, K.Q3 = 3 * Q, K.Qf = 28 * Q, K.Q10 = 10 * Q;
+    K.c = (uint32_t)((1ull << SF_K) - Q);
+    K.c2 = 2 * K.c;
+    return K;
+}
+}  // namespace
+
 hipError_t launch_blind_rotate_sf(const BRParams& P, const DevTables& T, const void* bsk, const void* sf,
                                   const uint64_t* a, uint64_t amod, uint64_t* acc, size_t B, hipStream_t s,
                                   const Knobs& kn, DuoDev* duo) {
     if (B == 0) return hipSuccess;
     if (!sf_path_supported(P, 64)) return hipErrorNotSupported;
-    SfC K;
-    K.Q = P.Q, K.Q3 = 3 * P.Q, K.Qf = 28 * P.Q, K.Q10 = 10 * P.Q;
-    K.c = (uint32_t)((1ull << SF_K) - P.Q);
-    K.c2 = 2 * K.c;
+    const SfC K = make_sf_const(P.Q);
     const uint64_t* w1 = (const uint64_t*)sf;
     const size_t lds = ((size_t)4 * G3_N + SF_MT) * 8 + rot_exponent_bytes(P.n);  // two polynomials, forward twiddles, monomial tables, a'_i
     const bool no_sf2 = !kn.sf2;  // gen3sf (cross-check)
@@ -1452,3 +1460,66 @@ hipError_t launch_blind_rotate_sf(const BRParams& P, const DevTables& T, const v
 }
 
 }  // namespace tfhe
+
+#ifdef TFHE_TEST_PROBES
+// ---- arithmetic probes (test library only; arith_probes.hpp, tests/test_gpu_arith_units.py) ----
+// op: 0 sf_mul(a, w0, w1)  1 sf_fold(x)  2 / 3 sf_ct<OFS = 0 / 1>(x, y, tab[i])  4 / 5 sf_gs<FOLD = 0 / 1>(x, y, tab[i])
+//     6 sf_add_acc(a, inc)  7 sf_digit(x, Qhalf, Klo, Khi, shift, sh)  8 sf_load_acc(v)
+//     9 / 10 sf_fwd_core<OFS = 0 / 1>(v[8], m0, g)  11 / 12 sf_inv_core<FOLD = 0 / 1>(v[8], m, g)
+// 10 words in, 8 out per case; tab = W0[T] then W1[T]
+#include "arith_probes.hpp"
+
+namespace tfhe {
+namespace {
+constexpr int SFP_NI = 10, SFP_NO = 8;
+__global__ void k_arith_sf(int op, size_t cases, const uint64_t* __restrict__ in, const uint64_t* __restrict__ tab,
+                           size_t tab_words, uint64_t* __restrict__ out, SfC K) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!probe_lane_runs(op, i, cases)) return;
+    const uint64_t* x = in + i * SFP_NI;
+    uint64_t* o = out + i * SFP_NO;
+    const size_t T = tab_words / 2;
+    const SfTw W{tab, tab + T};
+    const int f = op & 15;
+    if (f == 0) o[0] = sf_mul(x[0], x[1], x[2], K.c2);
+    else if (f == 1) o[0] = sf_fold(x[0], K.c);
+    else if (f >= 2 && f <= 5) {
+        if (x[2] >= T) return;
+        uint64_t a = x[0], b = x[1];
+        const uint32_t j = (uint32_t)x[2];
+        if (f == 2) sf_ct<false>(a, b, W, j, K);
+        else if (f == 3) sf_ct<true>(a, b, W, j, K);
+        else if (f == 4) sf_gs<false>(a, b, W, j, K);
+        else sf_gs<true>(a, b, W, j, K);
+        o[0] = a, o[1] = b;
+    } else if (f == 6) o[0] = sf_add_acc(x[0], x[1], K);
+    else if (f == 7) o[0] = (uint64_t)sf_digit(x[0], x[1], (int64_t)x[2], (int64_t)x[3], (uint32_t)x[4], (uint32_t)x[5]);
+    else if (f == 8) o[0] = sf_load_acc(x[0], K.Q);
+    else if (f >= 9 && f <= 12) {
+        uint64_t v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = x[k];
+        const uint64_t m = x[8], g = x[9];
+        if (m >= T || g >= T) return;
+        if (f <= 10) {
+            if (4 * m + 4 * g + 3 >= T) return;
+            if (f == 9) sf_fwd_core<false>(v, (uint32_t)m, (uint32_t)g, W, K);
+            else sf_fwd_core<true>(v, (uint32_t)m, (uint32_t)g, W, K);
+        } else {
+            if (m + 4 * g + 3 >= T) return;
+            if (f == 11) sf_inv_core<false>(v, (uint32_t)m, (uint32_t)g, W, K);
+            else sf_inv_core<true>(v, (uint32_t)m, (uint32_t)g, W, K);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = v[k];
+    }
+}
+}  // namespace
+}  // namespace tfhe
+
+extern "C" TFHE_ARITH_PROBE(sf) {
+    if ((op & 15) > 12 || Q >= (1ull << tfhe::SF_K) || Q <= (1ull << tfhe::SF_K) - (1ull << 20)) return -1;
+    return tfhe::probe_launch(tfhe::k_arith_sf, tfhe::SFP_NI, tfhe::SFP_NO, op, cases, in, in_words, tab, tab_words, out,
+                              out_words, tfhe::make_sf_const(Q));
+}
+#endif  // TFHE_TEST_PROBES

@@ -80,6 +80,8 @@ size_t bsk_fast_bytes(const BRParams& P);
 // build of the specialised kernel (see blind_rotate_fast.hip); 0 = default; false if unknown
 bool set_fast_variant(int v);
 int get_fast_variant();
+// the fast kernels' constants for modulus Q (out: a FastConst, blind_rotate_fast.hip / f4::FastConst)
+void fast_const_build(uint32_t Q, void* out);
 // 4-wavefront variant (blind_rotate_fast4.hip): its table block, packed behind the fast tables,
 // and its launch (K: the fast kernel's FastConst).  Digit shape: dig digits per polynomial
 // (dG2 = 2 dig), baseG = 2^logg, thr thrown digits, fold = top digit eliminated.

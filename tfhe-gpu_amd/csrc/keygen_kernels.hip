@@ -363,3 +363,43 @@ hipError_t launch_lwe_decrypt(uint32_t n, uint64_t qKS, const uint64_t* sk, size
 }
 
 }  // namespace tfhe
+
+#ifdef TFHE_TEST_PROBES
+// ---- arithmetic probes (test library only; arith_probes.hpp, tests/test_gpu_arith_units.py) ----
+// op: 0 addm64(a, b, m)  1 subm64(a, b, m)  2 to_mod(v, m)  3 centred(v, m)  4 mulmod_any(a, b, m)
+//     5 div128(hi, lo, d)  6 companion(v, Q) u64  7 companion(v, Q) u32  8 draw_at(state, k)
+// 3 words in, 1 out per case (the modulus travels with the case; Q is unused); no table
+#include "arith_probes.hpp"
+
+namespace tfhe {
+namespace {
+constexpr int KGP_NI = 3, KGP_NO = 1;
+__global__ void k_arith_kg(int op, size_t cases, const uint64_t* __restrict__ in, const uint64_t* __restrict__, size_t,
+                           uint64_t* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!probe_lane_runs(op, i, cases)) return;
+    const uint64_t* x = in + i * KGP_NI;
+    uint64_t r = 0;
+    switch (op & 15) {
+        case 0: r = addm64(x[0], x[1], x[2]); break;
+        case 1: r = subm64(x[0], x[1], x[2]); break;
+        case 2: r = to_mod((int64_t)x[0], x[1]); break;
+        case 3: r = (uint64_t)centred(x[0], x[1]); break;
+        case 4: r = mulmod_any(x[0], x[1], x[2]); break;
+        case 5: r = div128(x[0], x[1], x[2]); break;
+        case 6: r = companion(x[0], x[1]); break;
+        case 7: r = companion((uint32_t)x[0], (uint32_t)x[1]); break;
+        default: r = draw_at(x[0], x[1]); break;
+    }
+    out[i * KGP_NO] = r;
+}
+}  // namespace
+}  // namespace tfhe
+
+extern "C" TFHE_ARITH_PROBE(kg) {
+    (void)Q;
+    if ((op & 15) > 8) return -1;
+    return tfhe::probe_launch(tfhe::k_arith_kg, tfhe::KGP_NI, tfhe::KGP_NO, op, cases, in, in_words, tab, tab_words, out,
+                              out_words);
+}
+#endif  // TFHE_TEST_PROBES

@@ -11,12 +11,12 @@ CXX="/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contrac
 EXTRA="-DTFHE_TEST_PROBES"
 [ "$SRC" = blind_rotate_sf ] && EXTRA="$EXTRA -mllvm -pragma-unroll-threshold=100000"
 $CXX $EXTRA $DEFS -c csrc/$SRC.hip -o ../altlib/$TAG/alt.o
-# the test library's objects, with SRC's replaced (the probe builds of the sf / f64 files are the test ones)
+# the test library's objects, with SRC's replaced (sources with a _probes object contribute that one)
 OBJS=""
 for o in build/*.o; do
   b=$(basename $o .o)
+  [ -e build/${b}_probes.o ] && continue                              # product-only objects (the Makefile's PROBED)
   case $b in
-    blind_rotate_sf|blind_rotate_f64) continue ;;                    # product-only objects
     ${SRC}|${SRC}_probes) continue ;;                                 # replaced
   esac
   OBJS="$OBJS $o"

@@ -1,7 +1,9 @@
 """Worst-case magnitude walk of the wave-local FP64 blind rotation (k_blind_rotate_f64w,
 blind_rotate_f64.hip) for every reducing parameter set (RED: 2^40 <= Q < 2^50, i.e. STD128Q and
-STD128Q_OPT, Q = 2^50 - 2^14 + 1).  Every value is an integer held in a double, so every sum and
-every fmodmul operand must stay below 2^53.
+STD128Q_OPT, Q = 2^50 - 2^14 + 1) and for the non-reducing schedule (RED = false, instance
+<false, false, 2>: no fred inside the transforms) at the largest admitted Q below 2^40
+(2^40 - 36863, the largest prime = 1 mod 4096 there).  Every value is an integer held in a double, so
+every sum and every fmodmul operand must stay below 2^53, and every fmodmul product |a b| below 2^102.
 
 fmodmul(a, b), |a| <= A, |b| <= Bw:
     h = RN(ab)            |h| <= RN(A Bw)
@@ -23,13 +25,17 @@ The walk follows the kernel's schedule element by element (N = 2048, one polynom
            (k < 4) of passes C and B: a pass-A thread whose 8 inputs are all unreduced products then
            sums to 12 Q > 2^53 in the worst case (--round2 shows that walk);
   update   c + r (|c| <= Q/2) then fred.
-Exit 1 if any bound reaches 2^53.
+RED = false keeps the same schedule without the reductions inside the transforms (the freds of the
+monomial sum, the C' update and the accumulator update stay): a forward transform adds one product
+(<= ~Q/2) per stage, the inverse doubles its sums per stage up to 2^11 inputs (about 2^10 Q).
+Exit 1 if any bound reaches 2^53 (or a product 2^102).
 """
 import math
 import sys
 from fractions import Fraction
 
 LIM = 2.0 ** 53
+LIM_PROD = 2.0 ** 102
 N = 2048
 
 
@@ -44,6 +50,7 @@ class Arith:
         self.eps = abs(float(Fraction(qinv) * Q - 1))
         self.worst = 0.0
         self.where = ""
+        self.worst_prod = 0.0
 
     def note(self, x, where):
         if x > self.worst:
@@ -53,6 +60,7 @@ class Arith:
     def fmodmul(self, A, Bw, where=""):
         self.note(A, where + " (fmodmul operand)")
         P = A * Bw
+        self.worst_prod = max(self.worst_prod, P)
         h = P * (1 + 2.0 ** -53)
         hq = h / self.Q
         dt = hq * self.eps + ulp(hq * (1 + self.eps)) / 2
@@ -83,10 +91,12 @@ def forward(ar, x0, reduce_after_len=32):
 ROUND2 = "--round2" in sys.argv
 
 
-def inverse(ar, s0):
+def inverse(ar, s0, reducing=True):
     Qh = ar.Q / 2
     B = [s0] * N
-    if ROUND2:
+    if not reducing:
+        red = {}
+    elif ROUND2:
         red = {2: lambda x: (x & 3) in (0, 1), 16: lambda x: not (x >> 4) & 1, 128: lambda x: not (x >> 7) & 1}
     else:
         red = {2: lambda x: (x & 3) in (0, 1), 16: lambda x: True, 128: lambda x: True}
@@ -107,31 +117,39 @@ def inverse(ar, s0):
     return max(B)
 
 
-def walk(Q, LD):
+def walk(Q, LD, reducing=True):
     ar = Arith(Q)
     Qh = Q / 2
     F = ar.fred(Qh)  # a fred'ed value
-    d_out = max(forward(ar, 2.0 ** 24), forward(ar, Qh))  # digits; C' prologue and the WRAP digit (<= Q/2)
-    cx = ar.fred(ar.add(F, d_out))  # C' with the WRAP correction added
+    if reducing:
+        d_out = max(forward(ar, 2.0 ** 24), forward(ar, Qh))  # digits; C' prologue and the WRAP digit (<= Q/2)
+        cx = ar.fred(ar.add(F, d_out))  # C' with the WRAP correction added
+    else:
+        d_out = forward(ar, Qh, reduce_after_len=None)  # digits (<= G/2 < Q/2) and the C' prologue (|c| <= Q/2)
+        cx = max(F, ar.fmodmul(d_out, Qh, "C' prologue (N^-1)"))  # no WRAP instance below 2^40
     A = ar.add(*([ar.fmodmul(d_out, Qh, "products")] * (2 * LD) + [ar.fmodmul(cx, Qh, "products")] * 2),
                where="product sums")
     W = ar.fmodmul(Qh, Qh, "monomial table product") + 1
     sv = ar.fred(ar.add(ar.fmodmul(A, W, "monomial"), ar.fmodmul(A, W, "monomial"), where="monomial sum"))
     ar.fred(ar.add(F, sv, where="C' update"))
-    r = inverse(ar, sv)
+    r = inverse(ar, sv, reducing)
     ar.fred(ar.add(Qh, r, where="accumulator update"), "accumulator update")
     return ar, d_out, A, r
 
 
 def main():
     ok = True
-    for name, Q, LD in (("STD128Q / STD128Q_OPT", 2 ** 50 - 2 ** 14 + 1, 1),):
-        ar, d_out, A, r = walk(Q, LD)
+    for name, Q, LD, reducing in (("STD128Q / STD128Q_OPT", 2 ** 50 - 2 ** 14 + 1, 1, True),
+                                  ("RED = false at the largest Q < 2^40", 2 ** 40 - 36863, 2, False)):
+        if ROUND2 and not reducing:
+            continue  # (the round-2 schedule differed in the reductions only)
+        ar, d_out, A, r = walk(Q, LD, reducing)
         print(f"{name}: Q = 2^{math.log2(Q):.6f}, |RN(1/Q) Q - 1| = 2^{math.log2(ar.eps):.1f}")
         print(f"  forward outputs <= {d_out / Q:.3f} Q, product sums <= {A / Q:.3f} Q, inverse outputs <= {r / Q:.3f} Q")
         print(f"  largest operand or sum: {ar.worst / Q:.3f} Q = 2^{math.log2(ar.worst):.4f} at {ar.where}"
               f"  {'OK' if ar.worst < LIM else 'OVER 2^53'}")
-        ok &= ar.worst < LIM
+        print(f"  largest fmodmul product: 2^{math.log2(ar.worst_prod):.2f}  {'OK' if ar.worst_prod < LIM_PROD else 'OVER 2^102'}")
+        ok &= ar.worst < LIM and ar.worst_prod < LIM_PROD
     print("OK" if ok else "FAIL")
     sys.exit(0 if ok else 1)
 
