@@ -100,6 +100,28 @@ def eval_model(num_inputs, nodes, luts, outputs, q, values):
     return np.stack([w[o] for o in outputs]).astype(np.uint64)
 
 
+def node_value(eval_func, node, luts, q, x, y):
+    """One node on ciphertext rows x (and y, if it has a second term), int64 [instances, n+1]: the linear form
+    mod q (k on b only), then eval_func(ct, table) if it is a LUT node."""
+    op, _, _, c0, c1, lut, k = fields(node)
+    v = c0 * x + (c1 * y if c1 else 0)
+    v[:, -1] += k
+    v %= q
+    if op == "LUT":
+        v = eval_func(np.ascontiguousarray(v.astype(np.uint64)), np.ascontiguousarray(luts[lut])).astype(np.int64)
+    return v
+
+
+def compose(eval_func, num_inputs, nodes, luts, outputs, q, cts):
+    """cts[num_inputs, instances, n+1] -> [num_outputs, instances, n+1]: the netlist node by node in order with any
+    EvalFunc -- the GPU's vector API included -- for the LUT nodes, one call after the other."""
+    w = [np.asarray(c, dtype=np.int64) for c in cts]
+    for node in nodes:
+        _, in0, in1, _, c1, _, _ = fields(node)
+        w.append(node_value(eval_func, node, luts, q, w[in0], w[in1] if c1 else None))
+    return np.stack([w[o] for o in outputs]).astype(np.uint64)
+
+
 def oracle_netlist(orc, num_inputs, nodes, luts, outputs, q, cts):
     """cts[num_inputs, instances, n+1] -> [num_outputs, instances, n+1]: the oracle composed node by node.
 
@@ -108,18 +130,12 @@ def oracle_netlist(orc, num_inputs, nodes, luts, outputs, q, cts):
     order and wait only for earlier ones, so the oldest unfinished node can always run."""
     from concurrent.futures import ThreadPoolExecutor
 
-    def node_value(node, x, y):
-        op, in0, in1, c0, c1, lut, k = fields(node)
-        v = c0 * x.result() + (c1 * y.result() if c1 else 0)
-        v[:, -1] += k
-        v %= q
-        if op == "LUT":
-            v = orc.eval_func(np.ascontiguousarray(v.astype(np.uint64)), np.ascontiguousarray(luts[lut])).astype(np.int64)
-        return v
+    def run(node, x, y):
+        return node_value(orc.eval_func, node, luts, q, x.result(), y.result() if y is not None else None)
 
     with ThreadPoolExecutor(4) as pool:
         w = [pool.submit(np.asarray, c, np.int64) for c in cts]
         for node in nodes:
             _, in0, in1, _, c1, _, _ = fields(node)
-            w.append(pool.submit(node_value, node, w[in0], w[in1] if c1 else None))
+            w.append(pool.submit(run, node, w[in0], w[in1] if c1 else None))
         return np.stack([w[o].result() for o in outputs]).astype(np.uint64)
