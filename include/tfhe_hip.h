@@ -431,7 +431,7 @@ tfhe_status tfhe_rccl_selftest(int device, size_t bytes, const char* lib, int* v
 /* ---- launch knobs (no reference counterpart): the kernel-form choices earlier rounds measured A/B.
  * Read from the environment once, when a context is set up (TFHE_KS_TILED_MIN, TFHE_KS_CTS,
  * TFHE_KS_SPLIT, TFHE_KS_PK, TFHE_HOST_PARTS, TFHE_WIRE, TFHE_ACC_FLAGS, TFHE_F64W, TFHE_SF2,
- * TFHE_GENERIC, TFHE_DUO, TFHE_SF2P, TFHE_SPLIT4, TFHE_KS40, TFHE_TRACE); afterwards only tfhe_set_knobs changes them -- no
+ * TFHE_GENERIC, TFHE_DUO, TFHE_SF2P, TFHE_SPLIT4, TFHE_KS40, TFHE_PAIR_MIN, TFHE_TRACE); afterwards only tfhe_set_knobs changes them -- no
  * launch reads the environment.  Every setting computes the same outputs (each is a parity-tested
  * cross-check).  A variable that is not a whole number, or a value out of the field's range, fails
  * the setup with TFHE_ERR_INVALID_ARGUMENT (tfhe_set_knobs checks the same ranges).  tfhe_set_knobs
@@ -468,6 +468,18 @@ typedef struct tfhe_knobs {
 } tfhe_knobs;
 tfhe_status tfhe_get_knobs(tfhe_ctx* ctx, tfhe_knobs* out);
 tfhe_status tfhe_set_knobs(tfhe_ctx* ctx, const tfhe_knobs* in);
+
+/* One more launch knob, with calls of its own so that tfhe_knobs keeps its layout (new symbols only, same ABI
+ * version).  STD128-class contexts: device-resident batches of at least pair_min ciphertexts (default 3072,
+ * from TFHE_PAIR_MIN at setup; 0: never) run the blind rotation's pair instance -- two ciphertexts per
+ * wavefront, so every key row loaded feeds both -- unless the batch takes the two-group form (split4) or
+ * the host-array runner's completion flags.  Same outputs at every setting; tfhe_set_knobs leaves it alone.
+ * pair_launches (may be null, as may pair_min): blind rotations this context has launched on that instance. */
+tfhe_status tfhe_get_pair_min(tfhe_ctx* ctx, int32_t* pair_min, uint64_t* pair_launches);
+tfhe_status tfhe_set_pair_min(tfhe_ctx* ctx, int32_t pair_min);
+/* Dynamic LDS bytes per workgroup of the STD128 blind rotation: pair = 0 the default instance (four workgroups
+ * per CU), 1 the pair instance (three per CU: at most 160 KiB / 3). */
+size_t tfhe_fast4_lds_bytes(int pair);
 
 /* ---- extension (no reference counterpart): build of the specialised STD128-class blind
  * rotation used by later calls, for A/B runs and tests; 0 restores the default.  Process-wide;

@@ -86,7 +86,8 @@ size_t bsk_fast_bytes(const BRParams& P) { return ((size_t)P.n * 2 * P.dG2 * 2 *
 
 namespace {
 // TFHE_FAST_VARIANT / tfhe_set_kernel_variant select the build of the four-wavefront kernel:
-// 60 = default; 70 (two ciphertexts per wavefront) and 86 (four per workgroup) are kept as
+// 60 = default (batches from the pair_min launch setting on take 70's kernel); 70 (two ciphertexts per
+// wavefront: the pair instance at every batch size) and 86 (four per workgroup) are kept as
 // cross-checks of the multi-ciphertext paths (tests/test_gpu_kernel_variants.py).  The other
 // round-1/2 builds were removed in round 3.
 constexpr int kDefaultVariant = 60;
@@ -141,7 +142,9 @@ hipError_t launch_pack_bsk_fast(const BRParams& P, const DevTables& T, const voi
 }
 
 hipError_t launch_blind_rotate_fast(const BRParams& P, const DevTables&, const void* bsk_fast, const uint64_t* a,
-                                    uint64_t amod, uint64_t* acc, size_t B, hipStream_t s, BRDone* dn, int split_max) {
+                                    uint64_t amod, uint64_t* acc, size_t B, hipStream_t s, BRDone* dn, int split_max,
+                                    int pair_min, bool* paired) {
+    if (paired) *paired = false;
     if (B == 0) return hipSuccess;
     if (amod == 0 || (amod & (amod - 1)) || amod > 2 * FN) return hipErrorNotSupported;
     uint32_t loga = 0;
@@ -150,7 +153,7 @@ hipError_t launch_blind_rotate_fast(const BRParams& P, const DevTables&, const v
     fast_const_build((uint32_t)P.Q, &K);
     const int32_t* tabs = (const int32_t*)bsk_fast;
     return launch_blind_rotate_fast4(fast_variant(), fast_shape(P), &K, P.n, loga, tabs, tabs + TB_WORDS, a, acc, B, s,
-                                     dn, split_max);
+                                     dn, split_max, pair_min, paired);
 }
 
 // The kernels' constants for modulus Q (out: a FastConst); shared by the launcher above and the test library's

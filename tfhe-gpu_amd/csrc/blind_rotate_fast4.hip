@@ -20,7 +20,9 @@
 //    two (XB = 2: no barrier before the stores, 18 KiB more LDS; measured no faster).
 //  * Key rows stream through a ring: while the MAC consumes group g of one digit, group g of
 //    the next digit (or of the next round's C rows) is loaded into the freed registers, so
-//    every row has a whole transform to arrive.
+//    every row has a whole transform to arrive.  (RING = 2, the pair instance: a ring of two
+//    groups; groups 2 and 3 of a digit are loaded while its groups 0 and 1 are consumed, and the
+//    next round's first C rows after the monomial step: 16 fewer live registers.)
 //  * Twiddles of pass 4 are per-lane constants kept in registers, pass 0's are uniform
 //    (SGPRs), passes 1-3 come from LDS (ds_read_b128).  Pass 0 of a digit polynomial (7-bit
 //    inputs) reads all its products from three 128-entry LDS tables.
@@ -48,7 +50,14 @@ constexpr uint32_t L_TW = 0, L_TWI = P4F - P1F, L_MONO = 2 * L_TWI;  // passes 1
 // P4F: pass-4 forward twiddles, lane order (one ds_read_b128 per lane, conflict-free)
 constexpr uint32_t L_T1 = L_MONO + 2 * FN, L_T23 = L_T1 + 128, L_T2131 = L_T23 + 256, L_P4F = L_T2131 + 256;
 constexpr uint32_t LP = 304, XP = 1152, L_CT = L_P4F + 4 * 256;
-constexpr size_t lds_bytes(int P, int XB = 2, int CTS = 1) { return (size_t)(L_CT + CTS * (4 * P * LP + XB * P * XP)) * 4; }
+// P4: the pass-4 table area is reserved (every build but the pair instance, which needs three workgroups per CU
+// and keeps those twiddles in registers)
+constexpr uint32_t lds_ct(bool P4 = true) { return P4 ? L_CT : L_P4F; }
+constexpr size_t lds_bytes(int P, int XB = 2, int CTS = 1, bool P4 = true) {
+    return (size_t)(lds_ct(P4) + CTS * (4 * P * LP + XB * P * XP)) * 4;
+}
+// the pair instance <MINW = 3, NCT = 2>: two ciphertexts per wavefront at three workgroups per CU
+constexpr bool pair_build(int MINW, int NCT, int OPT) { return MINW == 3 && NCT == 2 && (OPT & 8) == 0; }
 
 struct Lay {
     int reg[2];
@@ -349,6 +358,7 @@ __device__ __forceinline__ void ntt_inv(int32_t (&X)[P][4], const int32_t* lds, 
 
 // NCT ciphertexts per wavefront (the same slots of each): every key row loaded feeds NCT
 // ciphertexts, halving the vector-memory traffic per bootstrap at NCT = 2.
+// RING: key-ring depth in groups, 4 (above) or 2.
 // OPT bit 0: T1 lookups in the digit transforms (bit 2: all of pass 0 from tables); bit 1: Barrett
 // accumulator update; bit 3: pass-4 forward twiddles from LDS
 // XB: cross-exchange areas (2: alternate, no barrier before the stores; 1: one area + a barrier)
@@ -368,7 +378,7 @@ __device__ __forceinline__ void ntt_inv(int32_t (&X)[P][4], const int32_t* lds, 
 // when THR = 0 and the top digit never wraps (the host checks); otherwise every digit is
 // transformed.  Pass 0's lookup tables hold digits in [-64, 64), so they need LOGG <= 7.
 template <int MINW, int NCT = 1, int EXP = 0, int OPT = 7, int XB = 2, int CTS = 1, int DIG = 4, int LOGG = 7,
-          int THR = 0, bool FOLD = true, bool FLAG = false, bool SPLIT = false>
+          int THR = 0, bool FOLD = true, bool FLAG = false, bool SPLIT = false, int RING = 4>
 __global__ void __launch_bounds__(TPC * (SPLIT ? 2 : CTS), MINW)
 k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __restrict__ tabs,
                      const int32_t* __restrict__ bsk, const uint64_t* __restrict__ a, uint64_t* __restrict__ acc_io,
@@ -378,6 +388,8 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
     constexpr int GR = SPLIT ? 2 : CTS;   // 256-thread groups per workgroup
     extern __shared__ __align__(16) int32_t lds[];
     static_assert(CTS == 1 || NCT == 1, "CTS > 1 needs NCT = 1");
+    static_assert(RING == 4 || RING == 2, "key ring of four groups or two");
+    constexpr uint32_t LCT = lds_ct(!pair_build(MINW, NCT, OPT));  // first word of the per-ciphertext regions
     static_assert(!SPLIT || (NCT == 1 && CTS == 1 && FOLD && !FLAG && XB == 1), "SPLIT: the folded one-ciphertext build");
     constexpr uint32_t RW = 2 * DIG;                  // key rows per (key, column)
     constexpr int TOP = DIG - 1;                       // FOLD: the eliminated digit (its rows: the C products)
@@ -401,7 +413,7 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
 
     LaneCtx C;
     constexpr uint32_t CTW = 4 * LOCW + XB * XAW;        // LDS words per ciphertext group
-    const uint32_t ctb = (L_CT + cl * CTW) * 4;         // bytes, uniform
+    const uint32_t ctb = (LCT + cl * CTW) * 4;          // bytes, uniform
     C.m_loc = ctb + w * LOCW * 4;
     C.g12 = C.m_loc + ld_lane<1, 2>(w, lane) * 4, C.g23 = C.m_loc + ld_lane<2, 3>(w, lane) * 4;
     C.g34 = C.m_loc + ld_lane<3, 4>(w, lane) * 4, C.g43 = C.m_loc + ld_lane<4, 3>(w, lane) * 4;
@@ -487,13 +499,19 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
             }
     };
 
-    v4i pw[4][2];  // key ring: the rows of the digit being consumed / about to be
+    v4i pw[RING][2];  // key ring: the rows of the digit being consumed / about to be
+    // RING = 2: after the products of group gi (slot gi & 1), groups 0 and 1 are followed by groups 2 and 3 of
+    // the same digit, groups 2 and 3 by groups 0 and 1 of the next one (nl at noff) while the round has `more`
+    auto step2 = [&](uint32_t off, int l, uint32_t noff, int nl, int gi, bool more) {
+        if (gi < 2) issue(pw[gi & 1], off, l, gi + 2);
+        else if (more) issue(pw[gi & 1], noff, nl, gi - 2);
+    };
     // FOLD: the C rows of round 0.  Otherwise digit 0's rows are issued at the start of each
     // round (not during the previous round's last products), so the ring is dead across the
     // monomial step and the inverse transform: fewer live registers (no spills in the loop).
     if constexpr (FOLD) {
 #pragma unroll
-        for (int gi = 0; gi < 4; ++gi) issue(pw[gi], 0, TOP, gi);
+        for (int gi = 0; gi < RING; ++gi) issue(pw[gi], 0, TOP, gi);
     }
 
     for (uint32_t i = 0; i < n; ++i) {
@@ -520,12 +538,13 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
 #pragma unroll
             for (int gi = 0; gi < 4; ++gi) {
                 __builtin_amdgcn_sched_barrier(0);
-                mac(s, Cp, pw[gi], gi, true);
-                issue(pw[gi], round_off, 0, gi);
+                mac(s, Cp, pw[gi % RING], gi, true);
+                if constexpr (RING == 4) issue(pw[gi], round_off, 0, gi);
+                else step2(round_off, TOP, round_off, 0, gi, true);
             }
         } else {
 #pragma unroll
-            for (int gi = 0; gi < 4; ++gi) issue(pw[gi], round_off, 0, gi);
+            for (int gi = 0; gi < RING; ++gi) issue(pw[gi], round_off, 0, gi);
         }
 #pragma unroll
         for (uint32_t l = 0; l < NT; ++l) {
@@ -557,8 +576,12 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
 #pragma unroll
             for (int gi = 0; gi < 4; ++gi) {
                 __builtin_amdgcn_sched_barrier(0);
-                mac(s, X, pw[gi], gi, !FOLD && l == 0);
-                if (FOLD || !last) issue(pw[gi], noff, nl, gi);
+                mac(s, X, pw[gi % RING], gi, !FOLD && l == 0);
+                if constexpr (RING == 4) {
+                    if (FOLD || !last) issue(pw[gi], noff, nl, gi);
+                } else {
+                    step2(round_off, (int)l, noff, nl, gi, !last);  // FOLD: the next C rows after the monomial step
+                }
             }
         }
 
@@ -569,7 +592,7 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
         if constexpr (SPLIT) {
             // partial sums of this polynomial's rows; the other column's go to the other group (LDS word
             // ((writer group * 2 + key) * 4 + r) * 256 + lane: conflict-free), this column's come back
-            int32_t* xch = lds + L_CT + GR * (4 * P * LP + XB * P * XP);
+            int32_t* xch = lds + LCT + GR * (4 * P * LP + XB * P * XP);
             const uint32_t bp = (et * ai[0]) & 2047, bn = (0u - bp) & 2047;
             const uint32_t F4p = ((bp >> 4) & 0x1C) | ((bp & 63) << 7), F4n = ((bn >> 4) & 0x1C) | ((bn & 63) << 7);
             const uint32_t hp = (bp >> 4) & 0x60, hn = (bn >> 4) & 0x60;
@@ -624,6 +647,11 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
                 for (int r = 0; r < 4; ++r) Cp[p][r] = smul(Cp[p][r], K.rM, K);
         }
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (FOLD && RING == 2) {  // the next round's first C rows: the inverse transform to arrive in
+            const uint32_t noff = (i + 1 < n ? i + 1 : i) * ROWB;
+            issue(pw[0], noff, TOP, 0), issue(pw[1], noff, TOP, 1);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         ntt_inv<XA1, P, EXP, PRE>(S, lds, C, K);
 #pragma unroll
         for (int q = 0; q < NCT; ++q)
@@ -717,6 +745,7 @@ __global__ void k_pack_tables4(uint32_t Q, const uint32_t* __restrict__ psi, con
 #ifndef TFHE_FAST4_KERNEL_ONLY
 
 size_t fast4_table_words() { return f4::T4_WORDS; }
+size_t fast4_lds_bytes(bool pair) { return pair ? f4::lds_bytes(4, 1, 1, false) : f4::lds_bytes(2, 1, 1); }
 
 hipError_t launch_pack_tables_fast4(uint32_t Q, const DevTables& T, void* out, hipStream_t s) {
     hipLaunchKernelGGL(f4::k_pack_tables4, dim3((f4::T4_WORDS + 255) / 256), dim3(256), 0, s, Q,
@@ -736,9 +765,13 @@ bool fast4_shape_supported(const Fast4Shape& sh) {
 hipError_t launch_blind_rotate_fast4_d6(const f4::FastConst& K, uint32_t n, uint32_t loga, const int32_t* tabs4,
                                         const int32_t* bsk, const uint64_t* a, uint64_t* acc, size_t B, hipStream_t s);
 
+// blind_rotate_fast4_pair.hip: two ciphertexts per wavefront at three workgroups per CU, built under max-ilp
+hipError_t launch_blind_rotate_fast4_pair(const f4::FastConst& K, uint32_t n, uint32_t loga, const int32_t* tabs4,
+                                          const int32_t* bsk, const uint64_t* a, uint64_t* acc, size_t B, hipStream_t s);
+
 hipError_t launch_blind_rotate_fast4(int variant, const Fast4Shape& sh, const void* K, uint32_t n, uint32_t loga,
                                      const int32_t* tabs4, const int32_t* bsk, const uint64_t* a, uint64_t* acc,
-                                     size_t B, hipStream_t s, BRDone* dn, int split_max) {
+                                     size_t B, hipStream_t s, BRDone* dn, int split_max, int pair_min, bool* paired) {
     const f4::FastConst Kc = *reinterpret_cast<const f4::FastConst*>(K);
     auto launch = [&](auto kern, int nct, int xb = 2, int cts = 1, uint32_t* done = nullptr) {
         const size_t lb = f4::lds_bytes(2 * nct, xb, cts);
@@ -772,8 +805,14 @@ hipError_t launch_blind_rotate_fast4(int variant, const Fast4Shape& sh, const vo
         dn->written = true;
         return hipGetLastError();
     }
+    // large batches, and variant 70 at every size: the pair instance (two ciphertexts per wavefront, each key
+    // row loaded feeds both).  A last, partly filled generation of its workgroups costs in proportion to its
+    // size (7680 against 8192 ciphertexts, profiles/pair), so the batch is not split between the two kernels.
+    if (variant == 70 || (variant == 60 && pair_min > 0 && B >= (size_t)pair_min)) {
+        if (paired) *paired = true;
+        return launch_blind_rotate_fast4_pair(Kc, n, loga, tabs4, bsk, a, acc, B, s);
+    }
     switch (variant) {  // cross-check builds (blind_rotate_fast.hip known_variant)
-        case 70: launch(f4::k_blind_rotate_fast4<2, 2>, 2); break;                    // two ciphertexts per wavefront
         case 86: launch(f4::k_blind_rotate_fast4<4, 1, 0, 7, 1, 4>, 1, 1, 4); break;  // four per workgroup
         default: launch(f4::k_blind_rotate_fast4<4, 1, 0, 7, 1>, 1, 1); break;  // = 60
     }

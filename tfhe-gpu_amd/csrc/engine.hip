@@ -195,6 +195,7 @@ struct tfhe_ctx {
     ArenaLayout layout{};
     std::vector<Device> devs;
     std::atomic<uint64_t> bootstraps{0};
+    std::atomic<uint64_t> pair_launches{0};  // blind rotations launched on fast4's pair instance (tfhe_get_pair_min)
     int replicate_method = TFHE_REPLICATE_NONE;
     double replicate_ms = 0;
     size_t max_chunk = 65536;  // the reference's max_bootstapping_num, bootstrapping.cuh:140
@@ -219,6 +220,7 @@ const char* knob_out_of_range(const Knobs& k) {
     if (k.generic < 0 || k.generic > 2) return "generic (TFHE_GENERIC) not in 0..2";
     if (k.duo < 0 || k.duo > 256) return "duo (TFHE_DUO) not in 0..256";
     if (k.split4 < 0) return "split4 (TFHE_SPLIT4) < 0";
+    if (k.pair_min < 0) return "pair_min (TFHE_PAIR_MIN) < 0";
     if (k.f64w != 1) return "f64w (TFHE_F64W): the slot-layout FP64 kernel it selected was retired in round 5 (must be 1)";
     for (int32_t v : {k.ks_pk, k.wire, k.acc_flags, k.sf2, k.sf2p, k.trace, k.ks40})
         if (v < 0 || v > 1) return "a 0/1 knob (TFHE_KS_PK, TFHE_WIRE, TFHE_ACC_FLAGS, TFHE_SF2, TFHE_SF2P, TFHE_KS40) "
@@ -261,6 +263,7 @@ Knobs knobs_from_env(std::string& bad) {
     num("TFHE_DUO", k.duo);
     num("TFHE_SF2P", k.sf2p);
     num("TFHE_SPLIT4", k.split4);
+    num("TFHE_PAIR_MIN", k.pair_min);
     num("TFHE_KS40", k.ks40);
     num("TFHE_GENERIC", k.generic);
     if (const char* e = std::getenv("TFHE_GENERIC_V1"); e && e[0] == '1') k.generic = 1;    // round-3 names
@@ -579,8 +582,10 @@ tfhe_status dev_blind_rotate(tfhe_ctx* c, Device& d, const uint64_t* a, uint64_t
     if (amod == 0 || (2ull * c->p.N) % amod != 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "a-modulus must divide 2N");
     const ArenaLayout& L = c->layout;
     if (c->use_fast && (amod & (amod - 1)) == 0) {
+        bool paired = false;
         HCHECK(launch_blind_rotate_fast(c->br, d.tables, d.bsk_fast, a, amod, acc, B, d.stream,
-                                        d.br_done.flags ? &d.br_done : nullptr, c->kn.split4));
+                                        d.br_done.flags ? &d.br_done : nullptr, c->kn.split4, c->kn.pair_min, &paired));
+        if (paired) c->pair_launches.fetch_add(1, std::memory_order_relaxed);
     } else if (c->use_f64) {
         HCHECK(launch_blind_rotate_f64(c->br, d.tables, d.keys_f64, c->f64_fold, a, amod, acc, B, d.stream, c->kn,
                                        d.duo.base ? &d.duo : nullptr));
@@ -2080,13 +2085,15 @@ tfhe_status tfhe_get_info(tfhe_ctx* c, tfhe_info* out) {
     });
 }
 
-static_assert(sizeof(tfhe_knobs) == sizeof(Knobs), "tfhe_knobs mirrors tfhe::Knobs field by field");
+// pair_min follows the mirrored fields (tfhe_knobs is fixed by the ABI version; tfhe_set_pair_min sets it)
+static_assert(sizeof(tfhe_knobs) == offsetof(Knobs, pair_min) && sizeof(Knobs) == sizeof(tfhe_knobs) + sizeof(int32_t),
+              "tfhe_knobs mirrors tfhe::Knobs field by field up to pair_min");
 
 tfhe_status tfhe_get_knobs(tfhe_ctx* c, tfhe_knobs* out) {
     return guarded([&]() -> tfhe_status {
         SCHECK(check_ctx(c));
         if (!out) return fail(TFHE_ERR_INVALID_ARGUMENT, "null output");
-        std::memcpy(out, &c->kn, sizeof(Knobs));
+        std::memcpy(out, &c->kn, sizeof(tfhe_knobs));
         return TFHE_OK;
     });
 }
@@ -2095,8 +2102,8 @@ tfhe_status tfhe_set_knobs(tfhe_ctx* c, const tfhe_knobs* in) {
     return guarded([&]() -> tfhe_status {
         SCHECK(check_ctx(c));
         if (!in) return fail(TFHE_ERR_INVALID_ARGUMENT, "null knobs");
-        Knobs k;
-        std::memcpy(&k, in, sizeof(Knobs));
+        Knobs k = c->kn;  // pair_min stays
+        std::memcpy(&k, in, sizeof(tfhe_knobs));
         if (const char* why = knob_out_of_range(k)) return fail(TFHE_ERR_INVALID_ARGUMENT, std::string("knob out of range: ") + why);
         if (k.probe != 0 && !f64_test_probes_compiled())
             return fail(TFHE_ERR_UNSUPPORTED, "probe builds exist only in the test library (libtfhe_hip_test.so)");
@@ -2104,6 +2111,26 @@ tfhe_status tfhe_set_knobs(tfhe_ctx* c, const tfhe_knobs* in) {
         return TFHE_OK;
     });
 }
+
+tfhe_status tfhe_get_pair_min(tfhe_ctx* c, int32_t* pair_min, uint64_t* pair_launches) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_ctx(c));
+        if (pair_min) *pair_min = c->kn.pair_min;
+        if (pair_launches) *pair_launches = c->pair_launches.load(std::memory_order_relaxed);
+        return TFHE_OK;
+    });
+}
+
+tfhe_status tfhe_set_pair_min(tfhe_ctx* c, int32_t pair_min) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_ctx(c));
+        if (pair_min < 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "knob out of range: pair_min (TFHE_PAIR_MIN) < 0");
+        c->kn.pair_min = pair_min;
+        return TFHE_OK;
+    });
+}
+
+size_t tfhe_fast4_lds_bytes(int pair) { return fast4_lds_bytes(pair != 0); }
 
 tfhe_status tfhe_shard_range(size_t total, int world, int rank, size_t* lo, size_t* hi) {
     if (world < 1 || rank < 0 || rank >= world || !lo || !hi) return fail(TFHE_ERR_INVALID_ARGUMENT, "bad world/rank");

@@ -36,6 +36,9 @@ struct Knobs {
     int32_t sf2p = 1;           // 0: sf2 with one ciphertext per workgroup instead of two (sf2p) above the duo batches
     int32_t split4 = 384;       // STD128 class: batches up to this size run fast4's two-group form (SPLIT); 0: never
     int32_t ks40 = 1;           // 8-byte keys with qKS = 2^(33..37): the tiled key switch on split-word records; 0: u64
+    // -- not in tfhe_knobs (whose layout is fixed by the ABI version): tfhe_set_pair_min / tfhe_get_pair_min --
+    int32_t pair_min = 3072;    // STD128 class: batches from this size run fast4's pair instance (two ciphertexts per
+                                // wavefront, blind_rotate_fast4_pair.hip); 0: never
 };
 
 // Device tables for one (Q, N), word type W (uint32_t or uint64_t storage).
@@ -69,9 +72,10 @@ hipError_t launch_blind_rotate_generic(int word_bits, const BRParams& P, const D
 // transforms, one wavefront per ciphertext.  Returns hipErrorNotSupported when the
 // parameters do not match its specialisation.
 // split_max: batches up to this size run the two-group form (k_blind_rotate_fast4 SPLIT; tfhe_knobs.split4)
+// pair_min: larger batches from this size run the pair instance (0: never); *paired: whether this launch did
 hipError_t launch_blind_rotate_fast(const BRParams& P, const DevTables& T, const void* bsk_fast, const uint64_t* a,
                                     uint64_t amod, uint64_t* acc, size_t B, hipStream_t s, BRDone* dn = nullptr,
-                                    int split_max = 0);
+                                    int split_max = 0, int pair_min = 0, bool* paired = nullptr);
 bool fast_path_supported(const BRParams& P, int word_bits);
 // Converts the generic device BSK and tables into the fast kernel's Montgomery form.
 hipError_t launch_pack_bsk_fast(const BRParams& P, const DevTables& T, const void* bsk, void* bsk_fast,
@@ -94,7 +98,9 @@ size_t fast4_table_words();
 hipError_t launch_pack_tables_fast4(uint32_t Q, const DevTables& T, void* out, hipStream_t s);
 hipError_t launch_blind_rotate_fast4(int variant, const Fast4Shape& sh, const void* K, uint32_t n, uint32_t loga,
                                      const int32_t* tabs4, const int32_t* bsk, const uint64_t* a, uint64_t* acc,
-                                     size_t B, hipStream_t s, BRDone* dn = nullptr, int split_max = 0);
+                                     size_t B, hipStream_t s, BRDone* dn = nullptr, int split_max = 0, int pair_min = 0,
+                                     bool* paired = nullptr);
+size_t fast4_lds_bytes(bool pair);  // dynamic LDS of the default / pair instance at the STD128 shape
 
 // Exact-FP64 blind rotation for 2^32 <= Q < 2^50, N = 2048 (STD192 / STD192Q / STD128Q classes):
 // keys/tables as centred doubles derived on device from the generic (u64) arena.

@@ -158,6 +158,9 @@ _SIGS = {
     "tfhe_host_selftest": ([P], C.c_int),
     "tfhe_get_knobs": ([VP, C.POINTER(Knobs)], C.c_int),
     "tfhe_set_knobs": ([VP, C.POINTER(Knobs)], C.c_int),
+    "tfhe_get_pair_min": ([VP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)], C.c_int),
+    "tfhe_set_pair_min": ([VP, C.c_int32], C.c_int),
+    "tfhe_fast4_lds_bytes": ([C.c_int], SZ),
 }
 
 

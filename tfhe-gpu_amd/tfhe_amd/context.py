@@ -190,12 +190,28 @@ class BinFHEContextHIP:
         return self._h
 
     # -- launch knobs (tfhe_knobs: environment at setup, then only these calls) --
+    # pair_min has calls of its own (tfhe_knobs keeps its layout); here it is one more knob.  A library
+    # without them (an earlier build in an A/B run) has no such knob.
     def knobs(self) -> dict:
         k = Knobs()
         self._check(self._L.tfhe_get_knobs(self._h, C.byref(k)), "tfhe_get_knobs")
-        return k.as_dict()
+        d = k.as_dict()
+        if hasattr(self._L, "tfhe_get_pair_min"):
+            v = C.c_int32()
+            self._check(self._L.tfhe_get_pair_min(self._h, C.byref(v), None), "tfhe_get_pair_min")
+            d["pair_min"] = v.value
+        return d
+
+    def pair_launches(self) -> int:
+        """Blind rotations this context has launched on the pair instance (two ciphertexts per wavefront)."""
+        n = C.c_uint64()
+        self._check(self._L.tfhe_get_pair_min(self._h, None, C.byref(n)), "tfhe_get_pair_min")
+        return n.value
 
     def set_knobs(self, **kw):
+        kw = dict(kw)
+        if "pair_min" in kw:
+            self._check(self._L.tfhe_set_pair_min(self._h, int(kw.pop("pair_min"))), "tfhe_set_pair_min")
         k = Knobs()
         self._check(self._L.tfhe_get_knobs(self._h, C.byref(k)), "tfhe_get_knobs")
         for name, v in kw.items():
