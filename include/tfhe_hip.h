@@ -178,7 +178,8 @@ tfhe_status tfhe_eval_acc_tv_rows(tfhe_ctx* ctx, size_t B, const uint64_t* const
                                   const uint64_t* tv, uint32_t tv_len, uint64_t* const* acc_rows);
 tfhe_status tfhe_mkm_switch_rows(tfhe_ctx* ctx, size_t B, const uint64_t* const* ext_a_rows, const uint64_t* ext_b,
                                  uint64_t fmod, uint64_t* const* out_a_rows, uint64_t* out_b);
-/* out[c] = sum_k matrix[k][c] * ct[k] mod modulus, c < cols: ct[K][n+1], matrix[K][cols], out[cols][n+1] */
+/* out[c] = sum_k matrix[k][c] * ct[k] mod modulus, c < cols: ct[K][n+1], matrix[K][cols], out[cols][n+1]
+ * (host arrays, device 0; tfhe_ciphertext_mul_matrix_device below with instances = 1) */
 tfhe_status tfhe_ciphertext_mul_matrix(tfhe_ctx* ctx, size_t K, const uint64_t* ct, size_t cols, const int64_t* matrix,
                                        uint64_t modulus, uint64_t* out);
 tfhe_status tfhe_lwe_gpu_setup(int num_gpus);
@@ -329,6 +330,39 @@ tfhe_status tfhe_eval_fcircuit_device(tfhe_ctx* ctx, const tfhe_fcircuit* c, siz
 /* the same on host arrays, staged through the context's first device */
 tfhe_status tfhe_eval_fcircuit(tfhe_ctx* ctx, const tfhe_fcircuit* c, size_t instances, const uint64_t* in,
                                uint64_t* out);
+
+/* ---- dense layers (no reference counterpart beyond CiphertextMulMatrix; new symbols only, the ABI version stays) ----
+ * The matrix product on device-resident buffers, for `instances` independent input sets that share one matrix, and
+ * the layer y = f(W^T x + b) on top of it: the product at modulus q, then EvalFunc with one shared table over the
+ * instances * cols results, every intermediate in HBM.
+ * Argument errors -- a null pointer other than d_bias / bias, instances, K or cols = 0, modulus = 0, a size product
+ * that overflows size_t; for tfhe_eval_dense*: q < 8, q not a power of two or q not dividing 2N -- are
+ * TFHE_ERR_INVALID_ARGUMENT, reported before any device call; a buffer on a device the context does not use is
+ * TFHE_ERR_INVALID_ARGUMENT as for the other _device calls. */
+/* d_ct[instances][K][n+1], d_matrix[K][cols] (shared), d_bias[cols] or NULL -> d_out[instances][cols][n+1]:
+ * out[i][c] = sum_k matrix[k][c] ct[i][k] mod modulus, bias[c] added to the b word only; exact at every modulus
+ * (signed entries by their residue; unreduced ciphertext words and bias entries are reduced).
+ * inputs are not written; device = the one holding d_out; ordered on `stream` */
+tfhe_status tfhe_ciphertext_mul_matrix_device(tfhe_ctx* ctx, size_t instances, size_t K, const uint64_t* d_ct,
+                                              size_t cols, const int64_t* d_matrix, const uint64_t* d_bias,
+                                              uint64_t modulus, uint64_t* d_out, void* stream);
+/* out[i][c] = EvalFunc(sum_k matrix[k][c] ct[i][k] + bias[c] mod q, lut): bit for bit what
+ * tfhe_ciphertext_mul_matrix (modulus q), an add of bias[c] to b, and tfhe_eval_func (shared table) give.
+ * d_lut: [q]; its first q words are read back once per call to classify it, as tfhe_eval_func_device; an
+ * arbitrary-class table with q > N is TFHE_ERR_UNSUPPORTED before anything is launched.  More than 65,536
+ * results run EvalFunc in slices, as a circuit level; tfhe_info.bootstraps grows by what tfhe_eval_func on
+ * instances * cols ciphertexts adds.  The pre-activation buffer and the matrix residues live in grow-only
+ * stores of the context: a call no larger than an earlier one allocates nothing. */
+tfhe_status tfhe_eval_dense_device(tfhe_ctx* ctx, size_t instances, size_t K, const uint64_t* d_ct, size_t cols,
+                                   const int64_t* d_matrix, const uint64_t* d_bias, uint64_t q,
+                                   const uint64_t* d_lut, uint64_t* d_out, void* stream);
+/* the same on host arrays, staged through the context's first device (pinned staging, as tfhe_eval_circuit) */
+tfhe_status tfhe_eval_dense(tfhe_ctx* ctx, size_t instances, size_t K, const uint64_t* ct, size_t cols,
+                            const int64_t* matrix, const uint64_t* bias, uint64_t q, const uint64_t* lut,
+                            uint64_t* out);
+/* the matrix-product kernel's tile sizes, for tests and tools: K-tile, column tile, threads per workgroup
+ * (any pointer may be NULL) */
+void tfhe_mm_tiles(int* kt, int* ct, int* threads);
 
 /* ---- key generation, encryption and decryption on the device (no reference counterpart; new symbols only, the
  * ABI version stays) ----

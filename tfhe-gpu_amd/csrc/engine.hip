@@ -156,6 +156,12 @@ struct Device {
     // run_device_op frame like the scratch.
     uint64_t* wires = nullptr;
     size_t wires_words = 0;
+    // The matrix product's stores, under the wire store's rules (ensure_words): the signed entries' residues,
+    // K cols words (k_mm_reduce_matrix), and the dense layer's pre-activation z, instances cols (n+1) words.
+    uint64_t* mm_mat = nullptr;
+    size_t mm_mat_words = 0;
+    uint64_t* dense_z = nullptr;
+    size_t dense_z_words = 0;
 };
 
 // hipMalloc'd buffer owned by one scope (error paths free it too)
@@ -468,6 +474,8 @@ void free_device(Device& d) {
     hipFree(d.keys_sf);
     hipFree(d.ks40);
     hipFree(d.wires);
+    hipFree(d.mm_mat);
+    hipFree(d.dense_z);
     hipFree(d.duo.base);
     if (d.duo.fence) hipEventDestroy(d.duo.fence);
     delete d.duo.mu;
@@ -774,13 +782,37 @@ tfhe_status dev_sign(tfhe_ctx* c, Device& d, const uint64_t* ct, uint64_t mod, u
 // The wire store of a run: grow-only; no queued kernel uses the old buffer once sc_fence has passed
 // (every user runs inside a run_device_op frame).  A failed allocation leaves the device without a store
 // and the context usable.
-tfhe_status ensure_wires(Device& d, size_t words) {
-    if (words <= d.wires_words) return TFHE_OK;
+tfhe_status ensure_words(Device& d, uint64_t*& buf, size_t& have, size_t words) {
+    if (words <= have) return TFHE_OK;
     if (d.sc_fence) HCHECK(hipEventSynchronize(d.sc_fence));
-    hipFree(d.wires);
-    d.wires = nullptr, d.wires_words = 0;
-    HCHECK(hipMalloc(&d.wires, words * sizeof(uint64_t)));
-    d.wires_words = words;
+    hipFree(buf);
+    buf = nullptr, have = 0;
+    HCHECK(hipMalloc(&buf, words * sizeof(uint64_t)));
+    have = words;
+    return TFHE_OK;
+}
+tfhe_status ensure_wires(Device& d, size_t words) { return ensure_words(d, d.wires, d.wires_words, words); }
+
+// ---------------------------------------------------------------------------
+// the matrix product and the dense layer on one device (inside run_device_op)
+// ---------------------------------------------------------------------------
+// out[i][c] = sum_k matrix[k][c] ct[i][k] (+ bias[c] on b) mod modulus; d.mm_mat holds K cols words
+tfhe_status dev_mul_matrix(tfhe_ctx* c, Device& d, size_t instances, size_t K, const uint64_t* ct, size_t cols,
+                           const int64_t* matrix, const uint64_t* bias, uint64_t modulus, uint64_t* out) {
+    HCHECK(launch_mul_matrix(c->p.n + 1, instances, K, ct, cols, matrix, bias, modulus, d.mm_mat, out, d.stream));
+    return TFHE_OK;
+}
+
+// z = W^T x + bias mod q into d.dense_z, then EvalFunc over the flat batch of instances cols ciphertexts in
+// slices of the scratch, as dev_circuit slices a level
+tfhe_status dev_dense(tfhe_ctx* c, Device& d, int prop, size_t instances, size_t K, const uint64_t* ct, size_t cols,
+                      const int64_t* matrix, const uint64_t* bias, uint64_t q, const uint64_t* d_lut, uint64_t* out) {
+    SCHECK(dev_mul_matrix(c, d, instances, K, ct, cols, matrix, bias, q, d.dense_z));
+    const size_t w = c->p.n + 1, total = instances * cols, slice = std::min(d.sc.cap, c->max_chunk);
+    for (size_t first = 0; first < total; first += slice) {
+        const size_t B = std::min(slice, total - first);
+        SCHECK(dev_func(c, d, prop, d.dense_z + first * w, q, d_lut, 0, out + first * w, B));
+    }
     return TFHE_OK;
 }
 
@@ -2622,6 +2654,65 @@ tfhe_status tfhe_eval_decomp(tfhe_ctx* c, size_t B, const uint64_t* ct, uint64_t
     });
 }
 
+extern "C++" {
+namespace {
+// what the matrix-product calls check of their sizes: none zero, no product that overflows size_t in bytes
+tfhe_status check_mm_sizes(tfhe_ctx* c, size_t instances, size_t K, size_t cols, uint64_t modulus) {
+    if (instances == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "CiphertextMulMatrix: no instances");
+    if (K == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "Input ciphertexts are empty.");
+    if (cols == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "Input matrix is empty.");
+    if (modulus == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "modulus is 0");
+    const size_t w = c->p.n + 1, lim = SIZE_MAX / sizeof(uint64_t);
+    if (K > lim / cols || K > lim / w || instances > lim / w / K || cols > lim / w || instances > lim / w / cols)
+        return fail(TFHE_ERR_INVALID_ARGUMENT, "CiphertextMulMatrix: sizes overflow");
+    return TFHE_OK;
+}
+
+// d_out selects the device; the residue store is in place before the frame opens
+tfhe_status mul_matrix_on_device(tfhe_ctx* c, size_t instances, size_t K, const uint64_t* d_ct, size_t cols,
+                                 const int64_t* d_matrix, const uint64_t* d_bias, uint64_t modulus, uint64_t* d_out,
+                                 void* stream) {
+    Device* dp = nullptr;
+    SCHECK(device_for(c, d_out, dp));
+    HCHECK(hipSetDevice(dp->id));
+    SCHECK(ensure_words(*dp, dp->mm_mat, dp->mm_mat_words, K * cols));
+    return run_device_op(c, 0, d_out, stream, [&](Device& d) {
+        return dev_mul_matrix(c, d, instances, K, d_ct, cols, d_matrix, d_bias, modulus, d_out);
+    });
+}
+
+tfhe_status check_dense_call(tfhe_ctx* c, size_t instances, size_t K, const void* ct, size_t cols, const void* matrix,
+                             uint64_t q, const void* lut, const void* out) {
+    SCHECK(check_ctx(c));
+    if (!ct || !matrix || !lut || !out) return fail(TFHE_ERR_INVALID_ARGUMENT, "null argument");
+    SCHECK(check_mm_sizes(c, instances, K, cols, q));
+    if (q < 8 || (q & (q - 1)) != 0 || (2ull * c->p.N) % q != 0)
+        return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalDense: q must be a power of two >= 8 that divides 2N");
+    return TFHE_OK;
+}
+
+// d_out selects the device; the table's class comes from its first q words, read back once
+tfhe_status dense_on_device(tfhe_ctx* c, size_t instances, size_t K, const uint64_t* d_ct, size_t cols,
+                            const int64_t* d_matrix, const uint64_t* d_bias, uint64_t q, const uint64_t* d_lut,
+                            uint64_t* d_out, void* stream) {
+    Device* dp = nullptr;
+    SCHECK(device_for(c, d_out, dp));
+    HCHECK(hipSetDevice(dp->id));
+    std::vector<uint64_t> lut0(q);
+    hipStream_t s = stream ? (hipStream_t)stream : dp->stream;
+    HCHECK(hipMemcpyAsync(lut0.data(), d_lut, q * 8, hipMemcpyDeviceToHost, s));
+    HCHECK(hipStreamSynchronize(s));
+    const int prop = check_input_function(lut0.data(), q, q);
+    if (prop == 2 && q > c->p.N) return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
+    SCHECK(ensure_words(*dp, dp->mm_mat, dp->mm_mat_words, K * cols));
+    SCHECK(ensure_words(*dp, dp->dense_z, dp->dense_z_words, instances * cols * (c->p.n + 1)));
+    return run_device_op(c, std::min(instances * cols, c->max_chunk), d_out, stream, [&](Device& d) {
+        return dev_dense(c, d, prop, instances, K, d_ct, cols, d_matrix, d_bias, q, d_lut, d_out);
+    });
+}
+}  // namespace
+}  // extern "C++"
+
 tfhe_status tfhe_ciphertext_mul_matrix(tfhe_ctx* c, size_t K, const uint64_t* ct, size_t cols, const int64_t* matrix,
                                        uint64_t modulus, uint64_t* out) {
     return guarded([&]() -> tfhe_status {
@@ -2629,6 +2720,7 @@ tfhe_status tfhe_ciphertext_mul_matrix(tfhe_ctx* c, size_t K, const uint64_t* ct
         if (K == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "Input ciphertexts are empty.");
         if (cols == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "Input matrix is empty.");
         if (!ct || !matrix || !out || modulus == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "null argument");
+        SCHECK(check_mm_sizes(c, 1, K, cols, modulus));
         const uint32_t w = c->p.n + 1;
         Device& d = c->devs[0];
         HCHECK(hipSetDevice(d.id));
@@ -2642,12 +2734,74 @@ tfhe_status tfhe_ciphertext_mul_matrix(tfhe_ctx* c, size_t K, const uint64_t* ct
         } drain{d.stream};
         HCHECK(hipMemcpyAsync(dct.p, ct, K * w * 8, hipMemcpyHostToDevice, d.stream));
         HCHECK(hipMemcpyAsync(dm.p, matrix, K * cols * 8, hipMemcpyHostToDevice, d.stream));
-        HCHECK(launch_ct_mul_matrix(w, K, dct.as<uint64_t>(), cols, dm.as<int64_t>(), modulus, dout.as<uint64_t>(),
-                                    d.stream));
+        SCHECK(ensure_words(d, d.mm_mat, d.mm_mat_words, K * cols));
+        hipStream_t s = d.stream;  // device 0's own frame (d_out would select among logical devices by id)
+        tfhe_status st = sc_acquire(d, s);
+        if (st == TFHE_OK)
+            st = dev_mul_matrix(c, d, 1, K, dct.as<uint64_t>(), cols, dm.as<int64_t>(), nullptr, modulus,
+                                dout.as<uint64_t>());
+        const tfhe_status rel = sc_release(d, s);
+        if (st != TFHE_OK) return st;
+        SCHECK(rel);
         HCHECK(hipMemcpyAsync(out, dout.p, cols * w * 8, hipMemcpyDeviceToHost, d.stream));
         HCHECK(hipStreamSynchronize(d.stream));
         return TFHE_OK;
     });
+}
+
+tfhe_status tfhe_ciphertext_mul_matrix_device(tfhe_ctx* c, size_t instances, size_t K, const uint64_t* d_ct,
+                                              size_t cols, const int64_t* d_matrix, const uint64_t* d_bias,
+                                              uint64_t modulus, uint64_t* d_out, void* stream) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_ctx(c));
+        if (!d_ct || !d_matrix || !d_out) return fail(TFHE_ERR_INVALID_ARGUMENT, "null argument");
+        SCHECK(check_mm_sizes(c, instances, K, cols, modulus));
+        return mul_matrix_on_device(c, instances, K, d_ct, cols, d_matrix, d_bias, modulus, d_out, stream);
+    });
+}
+
+tfhe_status tfhe_eval_dense_device(tfhe_ctx* c, size_t instances, size_t K, const uint64_t* d_ct, size_t cols,
+                                   const int64_t* d_matrix, const uint64_t* d_bias, uint64_t q, const uint64_t* d_lut,
+                                   uint64_t* d_out, void* stream) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_dense_call(c, instances, K, d_ct, cols, d_matrix, q, d_lut, d_out));
+        return dense_on_device(c, instances, K, d_ct, cols, d_matrix, d_bias, q, d_lut, d_out, stream);
+    });
+}
+
+tfhe_status tfhe_eval_dense(tfhe_ctx* c, size_t instances, size_t K, const uint64_t* ct, size_t cols,
+                            const int64_t* matrix, const uint64_t* bias, uint64_t q, const uint64_t* lut,
+                            uint64_t* out) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_dense_call(c, instances, K, ct, cols, matrix, q, lut, out));
+        // the class is known from the host table: refuse before anything is allocated or launched
+        if (check_input_function(lut, q, q) == 2 && q > c->p.N)
+            return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
+        Device& d = c->devs[0];
+        HCHECK(hipSetDevice(d.id));
+        const size_t w = c->p.n + 1, wi = instances * K * w, wm = K * cols, wo = instances * cols * w;
+        // one block: ct | matrix | bias | lut | out
+        DevBuf buf;
+        HCHECK(hipMalloc(&buf.p, (wi + wm + cols + q + wo) * sizeof(uint64_t)));
+        uint64_t *dct = buf.as<uint64_t>(), *dm = dct + wi, *db = dm + wm, *dl = db + cols, *dout = dl + q;
+        tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wi, d.stream);
+        if (st == TFHE_OK) st = h2d_staged(d, dm, flat_rows(reinterpret_cast<const uint64_t*>(matrix), cols), wm, d.stream);
+        if (st == TFHE_OK && bias) st = h2d_staged(d, db, flat_rows(bias, cols), cols, d.stream);
+        if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(lut, q), q, d.stream);
+        if (st == TFHE_OK)
+            st = dense_on_device(c, instances, K, dct, cols, reinterpret_cast<const int64_t*>(dm), bias ? db : nullptr, q,
+                                 dl, dout, nullptr);
+        if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
+        const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
+        if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalDense: ") + hipGetErrorString(e));
+        return st;
+    });
+}
+
+void tfhe_mm_tiles(int* kt, int* ct, int* threads) {
+    if (kt) *kt = MM_KT;
+    if (ct) *ct = MM_CT;
+    if (threads) *threads = MM_THREADS;
 }
 
 // GPULWEOperation::GPUSetup(numGPUs) (lwe-operation.cu:143-146) ignores numGPUs and works on device 0;

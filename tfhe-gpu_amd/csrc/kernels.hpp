@@ -284,9 +284,13 @@ hipError_t launch_lwe_encrypt(uint32_t n, uint64_t qKS, const uint64_t* sk, size
 hipError_t launch_lwe_decrypt(uint32_t n, uint64_t qKS, const uint64_t* sk, size_t B, const uint64_t* ct,
                               uint64_t ptxt_mod, uint64_t mod, int64_t* msg, hipStream_t s);
 
-// CiphertextMulMatrix: out[c][w] = sum_k matrix[k][c] * ct[k][w] mod modulus.
-// ct and matrix are device copies the launch reduces in place into [0, modulus).
-hipError_t launch_ct_mul_matrix(uint32_t width, size_t K, uint64_t* ct, size_t cols, int64_t* matrix,
-                                uint64_t modulus, uint64_t* out, hipStream_t s);
+// CiphertextMulMatrix (mul_matrix.hip): out[i][c][w] = (bias[c] [w == width - 1] + sum_k matrix[k][c] ct[i][k][w])
+// mod modulus; ct [instances][K][width], matrix [K][cols] shared, bias [cols] or null, out [instances][cols][width].
+// No input is written; mat_scratch (K cols words) receives the entries' residues.  Tile sizes: a workgroup of
+// MM_THREADS threads owns MM_THREADS words of one instance and MM_CT columns, the matrix in LDS tiles of MM_KT rows.
+constexpr int MM_THREADS = 256, MM_KT = 32, MM_CT = 16;
+hipError_t launch_mul_matrix(uint32_t width, size_t instances, size_t K, const uint64_t* ct, size_t cols,
+                             const int64_t* matrix, const uint64_t* bias, uint64_t modulus, uint64_t* mat_scratch,
+                             uint64_t* out, hipStream_t s);
 
 }  // namespace tfhe

@@ -4,7 +4,7 @@
 //   * test-vector construction (binfhe-base-scheme.cpp:1087-1145, 1147-1192)
 //   * RLWE -> LWE extraction (binfhe-base-scheme.cpp:664-672, 1201-1205)
 //   * LWE glue of the chained ops (lwe-pke.cpp:175-215, lwe-ciphertext.h:120-124)
-//   * CiphertextMulMatrix (lwe-operation.cu:50-137), exact integer form
+//   (CiphertextMulMatrix lives in mul_matrix.hip)
 #include "device_math.hpp"
 #include "kernels.hpp"
 
@@ -328,65 +328,6 @@ hipError_t launch_lwe_op(uint32_t op, uint32_t n, uint64_t m, uint64_t c, const 
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(k_lwe_op, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, op, n, m, c, x, y, out,
                        total);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// CiphertextMulMatrix: the reference computes the product as an FP64 DGEMM and
-// fmod (lwe-operation.cu:106-111), exact only while |sums| < 2^53 and non-negative;
-// here every operand is first reduced into [0, modulus) (signed matrix entries by
-// their mathematical residue), then the sum is exact: unreduced u128 accumulation
-// when K (modulus-1)^2 < 2^128, else a modular add per term.
-// ---------------------------------------------------------------------------
-__global__ void k_reduce_signed(int64_t* __restrict__ v, size_t count, uint64_t modulus) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    __int128 r = (__int128)v[i] % (__int128)modulus;
-    if (r < 0) r += modulus;
-    reinterpret_cast<uint64_t*>(v)[i] = (uint64_t)r;
-}
-
-__global__ void k_reduce_unsigned(uint64_t* __restrict__ v, size_t count, uint64_t modulus) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    v[i] %= modulus;
-}
-
-template <bool PER_TERM>
-__global__ void k_ct_mul_matrix(uint32_t width, size_t K, const uint64_t* __restrict__ ct, size_t cols,
-                                const uint64_t* __restrict__ mat, uint64_t modulus, uint64_t* __restrict__ out) {
-    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t c = blockIdx.y;
-    if (w >= width) return;
-    unsigned __int128 acc = 0;
-    for (size_t k = 0; k < K; ++k) {
-        const unsigned __int128 t = (unsigned __int128)mat[k * cols + c] * ct[k * width + w];
-        if (PER_TERM) {
-            acc += t % modulus;  // acc < modulus before, so no overflow
-            if (acc >= modulus) acc -= modulus;
-        } else {
-            acc += t;
-        }
-    }
-    out[c * width + w] = (uint64_t)(acc % modulus);
-}
-
-hipError_t launch_ct_mul_matrix(uint32_t width, size_t K, uint64_t* ct, size_t cols, int64_t* matrix,
-                                uint64_t modulus, uint64_t* out, hipStream_t s) {
-    if (K == 0 || cols == 0) return hipSuccess;
-    if (modulus == 0) return hipErrorInvalidValue;
-    const size_t nm = K * cols, nc = K * (size_t)width;
-    hipLaunchKernelGGL(k_reduce_signed, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, s, matrix, nm, modulus);
-    hipLaunchKernelGGL(k_reduce_unsigned, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, ct, nc, modulus);
-    const unsigned __int128 sq = (unsigned __int128)(modulus - 1) * (modulus - 1);
-    const bool per_term = sq != 0 && sq > ~(unsigned __int128)0 / K;
-    const uint64_t* m = reinterpret_cast<const uint64_t*>(matrix);
-    if (per_term)
-        hipLaunchKernelGGL(k_ct_mul_matrix<true>, dim3((width + 255) / 256, (unsigned)cols), dim3(256), 0, s, width,
-                           K, ct, cols, m, modulus, out);
-    else
-        hipLaunchKernelGGL(k_ct_mul_matrix<false>, dim3((width + 255) / 256, (unsigned)cols), dim3(256), 0, s,
-                           width, K, ct, cols, m, modulus, out);
     return hipGetLastError();
 }
 

@@ -144,6 +144,10 @@ _SIGS = {
     "tfhe_fcircuit_eval_plain": ([VP, SZ, VP, VP], C.c_int),
     "tfhe_eval_fcircuit_device": ([VP, VP, SZ, VP, VP, VP], C.c_int),
     "tfhe_eval_fcircuit": ([VP, VP, SZ, u64p, u64p], C.c_int),
+    "tfhe_ciphertext_mul_matrix_device": ([VP, SZ, SZ, VP, SZ, VP, VP, U64, VP, VP], C.c_int),
+    "tfhe_eval_dense_device": ([VP, SZ, SZ, VP, SZ, VP, VP, U64, VP, VP, VP], C.c_int),
+    "tfhe_eval_dense": ([VP, SZ, SZ, u64p, SZ, i64p, VP, U64, u64p, u64p], C.c_int),
+    "tfhe_mm_tiles": ([C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], None),
     "tfhe_keygen_device": ([P, U64, C.c_int, VP, VP, VP, C.POINTER(U64), VP], C.c_int),
     "tfhe_setup_keygen": ([C.POINTER(VP), P, U64, C.c_int, u64p, C.POINTER(U64)], C.c_int),
     "tfhe_encrypt_device": ([P, C.c_int, VP, SZ, VP, U64, U64, U64, VP, C.POINTER(U64), VP], C.c_int),
@@ -235,6 +239,13 @@ def params_from_logq(name: str, arb_func: bool, logQ: int, N: int = 0, baseG: in
     check(lib().tfhe_params_from_logq(PARAMSETS[name], int(arb_func), logQ, N, baseG, throw, C.byref(p)),
           "tfhe_params_from_logq")
     return p
+
+
+def mm_tiles() -> tuple[int, int, int]:
+    """(K-tile, column tile, threads per workgroup) of the matrix-product kernel (tfhe_mm_tiles)."""
+    kt, ct, th = C.c_int(), C.c_int(), C.c_int()
+    lib().tfhe_mm_tiles(C.byref(kt), C.byref(ct), C.byref(th))
+    return kt.value, ct.value, th.value
 
 
 def host_selftest(p: Params):

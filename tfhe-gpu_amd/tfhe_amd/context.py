@@ -365,6 +365,51 @@ class BinFHEContextHIP:
                                                       C.c_void_p(d_out), C.c_void_p(stream)),
                     "tfhe_eval_fcircuit_device")
 
+    # -- dense layers: y = f(W^T x + b), the matrix product then one shared-table EvalFunc, all on the device --
+    def EvalDense(self, cts, matrix, lut, bias=None, q=None):
+        """cts[instances, K, n+1] mod q (or [K, n+1]: one instance), matrix[K, cols] int64, lut[q], bias[cols] or None
+        -> [instances, cols, n+1] (or [cols, n+1]); host arrays staged through the context's first device."""
+        w, qq = self.params.n + 1, q or self.params.q
+        x = _u64(cts)
+        one = x.ndim == 2
+        if one:
+            x = x[None]
+        m = np.ascontiguousarray(matrix, dtype=np.int64)
+        if m.ndim != 2 or m.shape[0] == 0 or m.shape[1] == 0:
+            raise ValueError(f"EvalDense: matrix must be 2-D [K][cols] and not empty, got {m.shape}")
+        K, cols = m.shape
+        if x.ndim != 3 or x.shape[0] == 0 or x.shape[1] != K or x.shape[2] != w:
+            raise ValueError(f"EvalDense: expected shape (instances, {K}, {w}), got {x.shape}")
+        lut = _u64(lut)
+        if lut.shape != (qq,):
+            raise ValueError(f"EvalDense: LUT must have shape ({qq},), got {lut.shape}")
+        b = None
+        if bias is not None:
+            b = _u64(bias)
+            if b.shape != (cols,):
+                raise ValueError(f"EvalDense: bias must have shape ({cols},), got {b.shape}")
+        x = np.ascontiguousarray(x)
+        out = np.empty((x.shape[0], cols, w), dtype=np.uint64)
+        self._check(self._L.tfhe_eval_dense(self._h, x.shape[0], K, x.ravel(), cols, m.ravel(),
+                                            C.c_void_p(b.ctypes.data if b is not None else None), qq, lut, out.ravel()),
+                    "tfhe_eval_dense")
+        return out[0] if one else out
+
+    def EvalDenseDevice(self, instances, K, d_ct, cols, d_matrix, d_lut, d_out, d_bias=0, q=None, stream=0):
+        """d_ct[instances][K][n+1], d_matrix[K][cols] int64, d_lut[q], d_bias[cols] or 0 -> d_out[instances][cols][n+1],
+        device pointers."""
+        self._check(self._L.tfhe_eval_dense_device(self._h, instances, K, C.c_void_p(d_ct), cols, C.c_void_p(d_matrix),
+                                                   C.c_void_p(d_bias), q or self.params.q, C.c_void_p(d_lut),
+                                                   C.c_void_p(d_out), C.c_void_p(stream)), "tfhe_eval_dense_device")
+
+    def CiphertextMulMatrixDevice(self, instances, K, d_ct, cols, d_matrix, modulus, d_out, d_bias=0, stream=0):
+        """d_ct[instances][K][n+1], d_matrix[K][cols] int64 (shared), d_bias[cols] or 0 -> d_out[instances][cols][n+1];
+        no input is written."""
+        self._check(self._L.tfhe_ciphertext_mul_matrix_device(self._h, instances, K, C.c_void_p(d_ct), cols,
+                                                              C.c_void_p(d_matrix), C.c_void_p(d_bias), modulus,
+                                                              C.c_void_p(d_out), C.c_void_p(stream)),
+                    "tfhe_ciphertext_mul_matrix_device")
+
     # -- device-resident (pointers are integers, e.g. torch tensor.data_ptr()) --
     def EvalBinGateDevice(self, gate, B, d_ct1, d_ct2, d_out, q=None, stream=0):
         g = BINGATE[gate] if isinstance(gate, str) else int(gate)
