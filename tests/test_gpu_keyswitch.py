@@ -10,10 +10,14 @@ split-word records, u32 + u8 per key, and the u64-word form stays as the ks40 = 
 (not multiples of the 512/1024-ciphertext tiles) and include all-zero and all-(Q-1)
 extracts.  Random keys: bit-exactness does not need valid ones."""
 
+import re
+
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
+
+KS_LINE = re.compile(r"\[ks\] B=(\d+) key bytes=(\d+) .*nsplit=(\d+)")
 
 SETS = {
     "STD128": lambda m: m.params_from_set("STD128"),
@@ -64,14 +68,34 @@ def _with_min(ctx, value, fn):
         return fn()
 
 
+def _traced(ctx, capfd, fn, **knobs):
+    """fn's result under knobs with the trace knob on, and the (B, key bytes, nsplit) of every `[ks]` line the tiled
+    launches printed on stderr (none: the gather served the call)."""
+    capfd.readouterr()
+    with ctx.knobs_set(trace=1, **knobs):
+        out = fn()
+    return out, [tuple(int(x) for x in m.groups()) for m in KS_LINE.finditer(capfd.readouterr().err)]
+
+
 @pytest.mark.parametrize("B", [300, 1029])
-def test_tiled_keyswitch_equals_oracle(ks_ctx, B):
+def test_tiled_keyswitch_equals_oracle(ks_ctx, B, capfd):
+    """Also without the step split (ks_split = 1: the in-kernel finish instead of k_ks_combine); the trace lines
+    say which ran."""
     name, op, ctx, orc = ks_ctx
     ext = _ext(op, B, B)
     fmod = op.q
-    tiled = _with_min(ctx, "1", lambda: ctx.MKMSwitch(ext, fmod))
+    tiled, lines = _traced(ctx, capfd, lambda: ctx.MKMSwitch(ext, fmod), ks_tiled_min=1)
     gather = _with_min(ctx, "0", lambda: ctx.MKMSwitch(ext, fmod))
     assert np.array_equal(tiled, gather)
+    unsplit, lines1 = _traced(ctx, capfd, lambda: ctx.MKMSwitch(ext, fmod), ks_tiled_min=1, ks_split=1)
+    print(f"{name} B = {B}: [ks] (B, key bytes, nsplit) default {lines}, ks_split = 1 {lines1}")
+    assert np.array_equal(unsplit, gather)
+    assert lines and lines1  # every one of these contexts has a tiled build
+    assert all(z == 1 for _, _, z in lines1)
+    # by default 300 ciphertexts are at most two ciphertext tiles, under 200 blocks on every context here: ks_nsplit's
+    # first rule splits them whatever the device (at 1029 the count depends on its resident blocks: printed only)
+    if B == 300:
+        assert all(z > 1 for _, _, z in lines), lines
     # the oracle on a sample (all of them for the cheap STD128 key switch)
     idx = np.arange(B) if name == "STD128" else np.r_[0:6, B // 2 - 3:B // 2 + 3, B - 6:B]
     assert np.array_equal(tiled[idx], orc.mkm_switch(np.ascontiguousarray(ext[idx]), fmod))
@@ -128,19 +152,25 @@ def test_u16_keys_without_packed_sums(ks_ctx):
 
 @pytest.mark.parametrize("ks_ctx", ["ARB12"], indirect=True)
 @pytest.mark.parametrize("B", [2, 128, 1029])
-def test_split_word_keys_equal_u64_words(ks_ctx, B):
+def test_split_word_keys_equal_u64_words(ks_ctx, B, capfd):
     """8-byte keys with qKS = 2^35 (ARB12 / the logQ contexts; TOY_N8192 takes the gather): the tiled key
     switch on the split-word records (ks40 = 1, the default: u32 low word + u8 high part, high parts summed
-    as byte fields mod 2^3) equals the u64-word form, the gather and the oracle -- at B = 2 and 128 through
-    the step split (partial sums + k_ks_combine), at 1029 without it; the rows of maximal entries (qKS - 1)
-    put every byte field at its bound."""
+    as byte fields mod 2^3) equals the u64-word form, the gather and the oracle.  By default every one of these
+    batches runs through the step split (partial sums + k_ks_combine; 8 ways at 1029), so each form also runs with
+    ks_split = 1, the in-kernel finish; the trace lines are asserted to say so.  Every 97th KSK row is maximal
+    (qKS - 1); tests/test_gpu_keyswitch_edges.py puts the byte fields at their bound."""
     name, op, ctx, orc = ks_ctx
     assert op.qKS == (1 << 35) and ctx.knobs()["ks40"] == 1
     ext = _ext(op, B, 40 + B)
-    split40 = _with_min(ctx, "1", lambda: ctx.MKMSwitch(ext, op.q))
-    with ctx.knobs_set(ks40=0):
-        words = _with_min(ctx, "1", lambda: ctx.MKMSwitch(ext, op.q))
+    split40, l40 = _traced(ctx, capfd, lambda: ctx.MKMSwitch(ext, op.q), ks_tiled_min=1)
+    words, l64 = _traced(ctx, capfd, lambda: ctx.MKMSwitch(ext, op.q), ks_tiled_min=1, ks40=0)
     gather = _with_min(ctx, "0", lambda: ctx.MKMSwitch(ext, op.q))
     assert np.array_equal(split40, words) and np.array_equal(words, gather)
+    print(f"B = {B}: [ks] (B, key bytes, nsplit) split-word {l40}, u64 words {l64}")
+    assert l40 and l64 and all(kb == 5 and z > 1 for _, kb, z in l40) and all(kb == 8 and z > 1 for _, kb, z in l64)
+    for k40, kb in ((1, 5), (0, 8)):
+        unsplit, l1 = _traced(ctx, capfd, lambda: ctx.MKMSwitch(ext, op.q), ks_tiled_min=1, ks40=k40, ks_split=1)
+        assert np.array_equal(unsplit, gather), k40
+        assert l1 and all(b == kb and z == 1 for _, b, z in l1), (k40, l1)
     idx = np.unique(np.r_[0:min(B, 3), B - 1])
     assert np.array_equal(split40[idx], orc.mkm_switch(np.ascontiguousarray(ext[idx]), op.q))

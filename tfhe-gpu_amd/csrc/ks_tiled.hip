@@ -622,7 +622,8 @@ hipError_t launch_tiled(const KSParams& P, const void* kska, const void* kskb, c
     const uint32_t blocks = nct * ((ncol + 7) / 8) * 8;
     const uint32_t nsplit = ks_nsplit(P, blocks, B, kn, sizeof(KW) == 8, resident_blocks((const void*)k, lds));
     if (kn.trace)
-        std::fprintf(stderr, "[ks] B=%zu key bytes=%d blocks=%u resident=%zu nsplit=%u\n", B, (int)sizeof(KW), blocks,
+        std::fprintf(stderr, "[ks] B=%zu key bytes=%d sum bits=%d pk=%d cts=%d blocks=%u resident=%zu nsplit=%u\n", B,
+                     (int)sizeof(KW), PK ? 16 : 8 * (int)sizeof(ACC), (int)PK, CTS, blocks,
                      resident_blocks((const void*)k, lds), nsplit);
     hipLaunchKernelGGL(k, dim3(blocks * nsplit), dim3(KT), lds, s, P, (const KW*)kska, (const KW*)kskb, dig, bq, B, Bp,
                        nct, ncol, fmod, out, nsplit, part);
@@ -657,8 +658,9 @@ hipError_t launch_tiled40(const KSParams& P, const void* rec, const void* kskb, 
     const uint32_t blocks = nct * ((ncol + 7) / 8) * 8;
     const uint32_t nsplit = ks_nsplit(P, blocks, B, kn, true, resident_blocks((const void*)k, lds));
     if (kn.trace)
-        std::fprintf(stderr, "[ks] B=%zu key bytes=%d blocks=%u resident=%zu nsplit=%u\n", B, 5, blocks,
-                     resident_blocks((const void*)k, lds), nsplit);
+        // (sum bits: u64 low-word sums; the high parts are byte fields mod 2^hbits)
+        std::fprintf(stderr, "[ks] B=%zu key bytes=%d sum bits=%d pk=%d cts=%d blocks=%u resident=%zu nsplit=%u\n", B, 5,
+                     64, 0, CTS, blocks, resident_blocks((const void*)k, lds), nsplit);
     hipLaunchKernelGGL(k, dim3(blocks * nsplit), dim3(KT), lds, s, P, (const unsigned char*)rec, (const uint64_t*)kskb,
                        dig, bq, B, Bp, nct, ncol, fmod, out, nsplit, part, hbits);
     if (nsplit > 1) {
