@@ -364,6 +364,53 @@ tfhe_status tfhe_eval_dense(tfhe_ctx* ctx, size_t instances, size_t K, const uin
  * (any pointer may be NULL) */
 void tfhe_mm_tiles(int* kt, int* ct, int* threads);
 
+/* ---- convolution layers (no reference counterpart; new symbols only, the ABI version stays) ----
+ * Conv2d on ciphertexts with the im2col gather inside the matrix-product kernel (no im2col buffer exists), and the
+ * layer y = f(conv(x) + b) on top of it.  With Cg = c_in / groups, Og = c_out / groups and o = g Og + c:
+ *   out[i][o][oy][ox] = bias[o] (b word only) + sum_{ic < Cg, ky < kh, kx < kw}
+ *                       weight[o][ic][ky][kx] ct[i][g Cg + ic][oy stride_h - pad_h + ky][ox stride_w - pad_w + kx]
+ * mod modulus; a tap outside [0, h) x [0, w) is zero padding and contributes nothing.
+ * ct[instances][c_in][h][w][n+1], weight[c_out][c_in/groups][kh][kw] int64 (OIHW, shared by all instances),
+ * bias[c_out] or NULL -> out[instances][c_out][oh][ow][n+1], oh = (h + 2 pad_h - kh) / stride_h + 1 and ow likewise
+ * (integer division).  The output layout is the input layout, so convolutions chain, and it is what
+ * tfhe_eval_dense_device reads as [instances][c_out oh ow][n+1].  Exact at every modulus, by the rules of
+ * tfhe_ciphertext_mul_matrix_device with K = Cg kh kw terms per sum.  No input is written.
+ * Argument errors -- a null pointer other than the bias, instances = 0, a zero among c_in, h, w, c_out, kh, kw,
+ * stride_*, groups, groups not dividing c_in or c_out, pad_h >= kh, pad_w >= kw, kh > h + 2 pad_h, kw > w + 2 pad_w,
+ * modulus = 0, a size product that overflows size_t; for tfhe_eval_conv2d*: q < 8, q not a power of two or q not
+ * dividing 2N -- are TFHE_ERR_INVALID_ARGUMENT, reported before any device call, the message naming the field; a
+ * buffer on a device the context does not use is TFHE_ERR_INVALID_ARGUMENT as for the other _device calls. */
+typedef struct tfhe_conv2d {
+    uint32_t c_in, h, w;          /* input planes and their size */
+    uint32_t c_out, kh, kw;       /* output planes, window */
+    uint32_t stride_h, stride_w;  /* >= 1 */
+    uint32_t pad_h, pad_w;        /* zero rows / columns on each side: pad_h < kh, pad_w < kw */
+    uint32_t groups;              /* divides c_in and c_out; 1: full; c_in: depthwise */
+} tfhe_conv2d;
+
+/* host only, no GPU: validates the descriptor; oh, ow, K = (c_in / groups) kh kw (any pointer may be NULL) */
+tfhe_status tfhe_conv2d_shape(const tfhe_conv2d* d, uint32_t* oh, uint32_t* ow, size_t* K);
+/* the gathered product alone, at any modulus; device = the one holding d_out; ordered on `stream` */
+tfhe_status tfhe_ciphertext_conv2d_device(tfhe_ctx* ctx, const tfhe_conv2d* d, size_t instances, const uint64_t* d_ct,
+                                          const int64_t* d_weight, const uint64_t* d_bias, uint64_t modulus,
+                                          uint64_t* d_out, void* stream);
+/* the layer: the product at modulus q, then EvalFunc with one shared table d_lut[q] over the flat batch of
+ * instances c_out oh ow results, every intermediate in HBM: bit for bit what im2col, tfhe_ciphertext_mul_matrix per
+ * group (modulus q), an add of bias[o] to b, tfhe_eval_func and a transpose to plane-major order give.  The table
+ * is classified as in tfhe_eval_dense_device (an arbitrary-class table with q > N is TFHE_ERR_UNSUPPORTED before
+ * anything is launched); more than 65,536 results run EvalFunc in slices; tfhe_info.bootstraps grows by what
+ * tfhe_eval_func on instances c_out oh ow ciphertexts adds.  Uses the dense layer's grow-only stores. */
+tfhe_status tfhe_eval_conv2d_device(tfhe_ctx* ctx, const tfhe_conv2d* d, size_t instances, const uint64_t* d_ct,
+                                    const int64_t* d_weight, const uint64_t* d_bias, uint64_t q, const uint64_t* d_lut,
+                                    uint64_t* d_out, void* stream);
+/* the same on host arrays, staged through the context's first device as tfhe_eval_dense */
+tfhe_status tfhe_eval_conv2d(tfhe_ctx* ctx, const tfhe_conv2d* d, size_t instances, const uint64_t* ct,
+                             const int64_t* weight, const uint64_t* bias, uint64_t q, const uint64_t* lut,
+                             uint64_t* out);
+/* the kernel's tile sizes, for tests and tools: K-tile, output-plane tile, threads per workgroup, output positions
+ * per workgroup (any pointer may be NULL) */
+void tfhe_conv2d_tiles(int* kt, int* ct, int* threads, int* positions);
+
 /* ---- key generation, encryption and decryption on the device (no reference counterpart; new symbols only, the
  * ABI version stays) ----
  * FOR TESTS, BENCHMARKS AND REPRODUCIBLE EXPERIMENTS.  The generator is splitmix64 from a 64-bit seed: it

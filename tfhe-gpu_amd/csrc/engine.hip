@@ -816,6 +816,31 @@ tfhe_status dev_dense(tfhe_ctx* c, Device& d, int prop, size_t instances, size_t
     return TFHE_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Conv2d and the convolution layer on one device (inside run_device_op)
+// ---------------------------------------------------------------------------
+// out[i][o][oy][ox] = sum over the window of weight[o] ct[i] (+ bias[o] on b) mod modulus, gathered in the kernel;
+// d.mm_mat holds c_out K words
+tfhe_status dev_conv2d(tfhe_ctx* c, Device& d, const ConvGeom& g, size_t instances, const uint64_t* ct,
+                       const int64_t* weight, const uint64_t* bias, uint64_t modulus, uint64_t* out) {
+    HCHECK(launch_conv2d(c->p.n + 1, g, instances, ct, weight, bias, modulus, d.mm_mat, out, d.stream));
+    return TFHE_OK;
+}
+
+// z = conv(x) + bias mod q into d.dense_z, then EvalFunc over the flat batch of instances c_out oh ow ciphertexts
+// in slices, as dev_dense
+tfhe_status dev_conv_layer(tfhe_ctx* c, Device& d, int prop, const ConvGeom& g, size_t instances, const uint64_t* ct,
+                           const int64_t* weight, const uint64_t* bias, uint64_t q, const uint64_t* d_lut,
+                           uint64_t* out) {
+    SCHECK(dev_conv2d(c, d, g, instances, ct, weight, bias, q, d.dense_z));
+    const size_t w = c->p.n + 1, total = instances * g.c_out * g.oh * g.ow, slice = std::min(d.sc.cap, c->max_chunk);
+    for (size_t first = 0; first < total; first += slice) {
+        const size_t B = std::min(slice, total - first);
+        SCHECK(dev_func(c, d, prop, d.dense_z + first * w, q, d_lut, 0, out + first * w, B));
+    }
+    return TFHE_OK;
+}
+
 void circuit_plan_free(int device, void* base) {
     int cur = 0;
     const bool have = hipGetDevice(&cur) == hipSuccess;
@@ -2802,6 +2827,177 @@ void tfhe_mm_tiles(int* kt, int* ct, int* threads) {
     if (kt) *kt = MM_KT;
     if (ct) *ct = MM_CT;
     if (threads) *threads = MM_THREADS;
+}
+
+extern "C++" {
+namespace {
+// the descriptor's own rules (no context, no device): every message names the field
+tfhe_status conv_geometry(const tfhe_conv2d* d, ConvGeom& g, size_t& K) {
+    const auto bad = [](const std::string& what) { return fail(TFHE_ERR_INVALID_ARGUMENT, "Conv2d: " + what); };
+    if (!d) return bad("null descriptor");
+    const struct {
+        uint32_t v;
+        const char* name;
+    } nonzero[] = {{d->c_in, "c_in"}, {d->h, "h"}, {d->w, "w"}, {d->c_out, "c_out"}, {d->kh, "kh"}, {d->kw, "kw"},
+                   {d->stride_h, "stride_h"}, {d->stride_w, "stride_w"}, {d->groups, "groups"}};
+    for (const auto& f : nonzero)
+        if (f.v == 0) return bad(std::string(f.name) + " is 0");
+    if (d->c_in % d->groups != 0) return bad("groups does not divide c_in");
+    if (d->c_out % d->groups != 0) return bad("groups does not divide c_out");
+    if (d->pad_h >= d->kh) return bad("pad_h must be below kh");
+    if (d->pad_w >= d->kw) return bad("pad_w must be below kw");
+    if (d->kh > (uint64_t)d->h + 2ull * d->pad_h) return bad("kh exceeds h + 2 pad_h");
+    if (d->kw > (uint64_t)d->w + 2ull * d->pad_w) return bad("kw exceeds w + 2 pad_w");
+    const uint64_t oh = ((uint64_t)d->h + 2ull * d->pad_h - d->kh) / d->stride_h + 1,
+                   ow = ((uint64_t)d->w + 2ull * d->pad_w - d->kw) / d->stride_w + 1;
+    if (oh > UINT32_MAX) return bad("h + 2 pad_h overflows");
+    if (ow > UINT32_MAX) return bad("w + 2 pad_w overflows");
+    g = ConvGeom{d->c_in, d->h, d->w, d->c_out, d->kh, d->kw, d->stride_h, d->stride_w, d->pad_h, d->pad_w, d->groups,
+                 (uint32_t)oh, (uint32_t)ow};
+    const uint64_t khw = (uint64_t)d->kh * d->kw;  // below 2^64
+    const size_t Cg = d->c_in / d->groups;
+    if (khw > SIZE_MAX / Cg) return bad("c_in kh kw overflows");
+    K = (size_t)(Cg * khw);
+    return TFHE_OK;
+}
+
+// acc *= f unless that leaves size_t
+bool conv_mul(size_t& acc, size_t f) {
+    if (f != 0 && acc > SIZE_MAX / f) return false;
+    acc *= f;
+    return true;
+}
+
+// what the convolution calls check before any device call; d_bias may be null
+tfhe_status check_conv_call(tfhe_ctx* c, const tfhe_conv2d* desc, size_t instances, const void* ct, const void* weight,
+                            uint64_t modulus, const void* out, ConvGeom& g, size_t& K) {
+    SCHECK(check_ctx(c));
+    if (!desc) return fail(TFHE_ERR_INVALID_ARGUMENT, "Conv2d: null descriptor");
+    if (!ct) return fail(TFHE_ERR_INVALID_ARGUMENT, "Conv2d: null ct");
+    if (!weight) return fail(TFHE_ERR_INVALID_ARGUMENT, "Conv2d: null weight");
+    if (!out) return fail(TFHE_ERR_INVALID_ARGUMENT, "Conv2d: null out");
+    if (instances == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "Conv2d: instances is 0");
+    SCHECK(conv_geometry(desc, g, K));
+    if (modulus == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "Conv2d: modulus is 0");
+    const size_t w = c->p.n + 1;
+    size_t in = sizeof(uint64_t), res = sizeof(uint64_t), wt = sizeof(uint64_t);
+    const bool ok = conv_mul(in, instances) && conv_mul(in, g.c_in) && conv_mul(in, g.h) && conv_mul(in, g.w) &&
+                    conv_mul(in, w) && conv_mul(res, instances) && conv_mul(res, g.c_out) && conv_mul(res, g.oh) &&
+                    conv_mul(res, g.ow) && conv_mul(res, w) && conv_mul(wt, g.c_out) && conv_mul(wt, K);
+    if (!ok) return fail(TFHE_ERR_INVALID_ARGUMENT, "Conv2d: sizes overflow");
+    return TFHE_OK;
+}
+
+tfhe_status check_conv_layer_call(tfhe_ctx* c, const tfhe_conv2d* desc, size_t instances, const void* ct,
+                                  const void* weight, uint64_t q, const void* lut, const void* out, ConvGeom& g,
+                                  size_t& K) {
+    SCHECK(check_conv_call(c, desc, instances, ct, weight, q, out, g, K));
+    if (!lut) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalConv2d: null lut");
+    if (q < 8 || (q & (q - 1)) != 0 || (2ull * c->p.N) % q != 0)
+        return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalConv2d: q must be a power of two >= 8 that divides 2N");
+    return TFHE_OK;
+}
+
+// d_out selects the device; the table's class comes from its first q words, read back once
+tfhe_status conv_layer_on_device(tfhe_ctx* c, const ConvGeom& g, size_t K, size_t instances, const uint64_t* d_ct,
+                                 const int64_t* d_weight, const uint64_t* d_bias, uint64_t q, const uint64_t* d_lut,
+                                 uint64_t* d_out, void* stream) {
+    Device* dp = nullptr;
+    SCHECK(device_for(c, d_out, dp));
+    HCHECK(hipSetDevice(dp->id));
+    std::vector<uint64_t> lut0(q);
+    hipStream_t s = stream ? (hipStream_t)stream : dp->stream;
+    HCHECK(hipMemcpyAsync(lut0.data(), d_lut, q * 8, hipMemcpyDeviceToHost, s));
+    HCHECK(hipStreamSynchronize(s));
+    const int prop = check_input_function(lut0.data(), q, q);
+    if (prop == 2 && q > c->p.N) return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
+    const size_t total = instances * g.c_out * g.oh * g.ow;
+    SCHECK(ensure_words(*dp, dp->mm_mat, dp->mm_mat_words, K * g.c_out));
+    SCHECK(ensure_words(*dp, dp->dense_z, dp->dense_z_words, total * (c->p.n + 1)));
+    return run_device_op(c, std::min(total, c->max_chunk), d_out, stream, [&](Device& d) {
+        return dev_conv_layer(c, d, prop, g, instances, d_ct, d_weight, d_bias, q, d_lut, d_out);
+    });
+}
+}  // namespace
+}  // extern "C++"
+
+tfhe_status tfhe_conv2d_shape(const tfhe_conv2d* d, uint32_t* oh, uint32_t* ow, size_t* K) {
+    return guarded([&]() -> tfhe_status {
+        ConvGeom g;
+        size_t k = 0;
+        SCHECK(conv_geometry(d, g, k));
+        if (oh) *oh = g.oh;
+        if (ow) *ow = g.ow;
+        if (K) *K = k;
+        return TFHE_OK;
+    });
+}
+
+tfhe_status tfhe_ciphertext_conv2d_device(tfhe_ctx* c, const tfhe_conv2d* desc, size_t instances, const uint64_t* d_ct,
+                                          const int64_t* d_weight, const uint64_t* d_bias, uint64_t modulus,
+                                          uint64_t* d_out, void* stream) {
+    return guarded([&]() -> tfhe_status {
+        ConvGeom g;
+        size_t K = 0;
+        SCHECK(check_conv_call(c, desc, instances, d_ct, d_weight, modulus, d_out, g, K));
+        Device* dp = nullptr;
+        SCHECK(device_for(c, d_out, dp));
+        HCHECK(hipSetDevice(dp->id));
+        SCHECK(ensure_words(*dp, dp->mm_mat, dp->mm_mat_words, K * g.c_out));
+        return run_device_op(c, 0, d_out, stream, [&](Device& d) {
+            return dev_conv2d(c, d, g, instances, d_ct, d_weight, d_bias, modulus, d_out);
+        });
+    });
+}
+
+tfhe_status tfhe_eval_conv2d_device(tfhe_ctx* c, const tfhe_conv2d* desc, size_t instances, const uint64_t* d_ct,
+                                    const int64_t* d_weight, const uint64_t* d_bias, uint64_t q, const uint64_t* d_lut,
+                                    uint64_t* d_out, void* stream) {
+    return guarded([&]() -> tfhe_status {
+        ConvGeom g;
+        size_t K = 0;
+        SCHECK(check_conv_layer_call(c, desc, instances, d_ct, d_weight, q, d_lut, d_out, g, K));
+        return conv_layer_on_device(c, g, K, instances, d_ct, d_weight, d_bias, q, d_lut, d_out, stream);
+    });
+}
+
+tfhe_status tfhe_eval_conv2d(tfhe_ctx* c, const tfhe_conv2d* desc, size_t instances, const uint64_t* ct,
+                             const int64_t* weight, const uint64_t* bias, uint64_t q, const uint64_t* lut,
+                             uint64_t* out) {
+    return guarded([&]() -> tfhe_status {
+        ConvGeom g;
+        size_t K = 0;
+        SCHECK(check_conv_layer_call(c, desc, instances, ct, weight, q, lut, out, g, K));
+        // the class is known from the host table: refuse before anything is allocated or launched
+        if (check_input_function(lut, q, q) == 2 && q > c->p.N)
+            return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
+        Device& d = c->devs[0];
+        HCHECK(hipSetDevice(d.id));
+        const size_t w = c->p.n + 1, wi = instances * g.c_in * g.h * g.w * w, wm = K * g.c_out, nb = g.c_out,
+                     wo = instances * g.c_out * g.oh * g.ow * w;
+        // one block: ct | weight | bias | lut | out
+        DevBuf buf;
+        HCHECK(hipMalloc(&buf.p, (wi + wm + nb + q + wo) * sizeof(uint64_t)));
+        uint64_t *dct = buf.as<uint64_t>(), *dm = dct + wi, *db = dm + wm, *dl = db + nb, *dout = dl + q;
+        tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wi, d.stream);
+        if (st == TFHE_OK) st = h2d_staged(d, dm, flat_rows(reinterpret_cast<const uint64_t*>(weight), K), wm, d.stream);
+        if (st == TFHE_OK && bias) st = h2d_staged(d, db, flat_rows(bias, nb), nb, d.stream);
+        if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(lut, q), q, d.stream);
+        if (st == TFHE_OK)
+            st = conv_layer_on_device(c, g, K, instances, dct, reinterpret_cast<const int64_t*>(dm), bias ? db : nullptr,
+                                      q, dl, dout, nullptr);
+        if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
+        const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
+        if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalConv2d: ") + hipGetErrorString(e));
+        return st;
+    });
+}
+
+void tfhe_conv2d_tiles(int* kt, int* ct, int* threads, int* positions) {
+    if (kt) *kt = CV_KT;
+    if (ct) *ct = CV_CT;
+    if (threads) *threads = CV_THREADS;
+    if (positions) *positions = CV_P;
 }
 
 // GPULWEOperation::GPUSetup(numGPUs) (lwe-operation.cu:143-146) ignores numGPUs and works on device 0;

@@ -293,4 +293,20 @@ hipError_t launch_mul_matrix(uint32_t width, size_t instances, size_t K, const u
                              const int64_t* matrix, const uint64_t* bias, uint64_t modulus, uint64_t* mat_scratch,
                              uint64_t* out, hipStream_t s);
 
+// Conv2d on ciphertexts (conv2d.hip): the matrix product with the im2col gather inside the kernel.
+// ct [instances][c_in][h][w][width], weight [c_out][c_in/groups][kh][kw] int64 (OIHW) shared, bias [c_out] or null,
+// out [instances][c_out][oh][ow][width]; a tap in the zero padding contributes nothing.  No input is written;
+// mat_scratch (c_out K words, K = (c_in/groups) kh kw) receives the weights' residues, reordered.  The geometry
+// is validated by the caller (tfhe_conv2d_shape).  Tile sizes: a workgroup of CV_THREADS threads owns CV_THREADS
+// words of one instance, CV_CT output planes of one group and CV_P output positions, the weights in LDS tiles of
+// CV_KT taps.
+constexpr int CV_THREADS = 256, CV_KT = 32, CV_CT = 8, CV_P = 2;
+struct ConvGeom {
+    uint32_t c_in, h, w, c_out, kh, kw, sh, sw, ph, pw, groups;
+    uint32_t oh, ow;  // (h + 2 ph - kh) / sh + 1, (w + 2 pw - kw) / sw + 1
+};
+hipError_t launch_conv2d(uint32_t width, const ConvGeom& g, size_t instances, const uint64_t* ct,
+                         const int64_t* weight, const uint64_t* bias, uint64_t modulus, uint64_t* mat_scratch,
+                         uint64_t* out, hipStream_t s);
+
 }  // namespace tfhe

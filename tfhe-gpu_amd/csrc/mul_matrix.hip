@@ -24,17 +24,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <type_traits>
 
 #include "kernels.hpp"
+#include "mm_arith.hpp"
 
 namespace tfhe {
 
 namespace {
-
-using u128 = unsigned __int128;
-
-enum MmMode { MM_M32 = 0, MM_M64 = 1, MM_GEN = 2, MM_GEN_TERM = 3 };
 
 // signed entries -> residues: a power-of-two modulus masks the two's-complement word, any other takes the
 // mathematical residue through __int128
@@ -51,18 +47,6 @@ __global__ void k_mm_reduce_matrix(const int64_t* __restrict__ mat, size_t count
         out[i] = (uint64_t)r;
     }
 }
-
-// (a + b) mod m for a, b < m <= 2^64 - 1 (the sum may carry out of 64 bits)
-__device__ __forceinline__ uint64_t mm_addm(uint64_t a, uint64_t b, uint64_t m) {
-    const uint64_t s = a + b;
-    return (s < a || s >= m) ? s - m : s;
-}
-
-template <int MODE>
-struct MmTypes {
-    using Tile = std::conditional_t<MODE == MM_M32, uint32_t, uint64_t>;
-    using Acc = std::conditional_t<MODE == MM_M32, uint32_t, std::conditional_t<MODE == MM_GEN, u128, uint64_t>>;
-};
 
 // grid: x = column tile, y = block of MM_THREADS words, z = instance
 template <int MODE>
@@ -147,13 +131,7 @@ hipError_t launch_mul_matrix(uint32_t width, size_t instances, size_t K, const u
     const size_t col_tiles = (cols + MM_CT - 1) / MM_CT, w_blocks = ((size_t)width + MM_THREADS - 1) / MM_THREADS;
     if (col_tiles > 0x7fffffffull || w_blocks > 65535) return hipErrorInvalidValue;
     const bool pow2 = (modulus & (modulus - 1)) == 0;
-    int mode;
-    if (pow2) {
-        mode = modulus <= (1ull << 32) ? MM_M32 : MM_M64;
-    } else {
-        const u128 sq = (u128)(modulus - 1) * (modulus - 1);
-        mode = (sq != 0 && sq > ~(u128)0 / K) ? MM_GEN_TERM : MM_GEN;
-    }
+    const int mode = mm_mode_for(modulus, K);
     const size_t nm = K * cols;
     hipLaunchKernelGGL(k_mm_reduce_matrix, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, s, matrix, nm, modulus,
                        (int)pow2, mat_scratch);

@@ -89,6 +89,15 @@ class FuncCircuitInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Conv2d(C.Structure):
+    """tfhe_conv2d: the geometry of a convolution (include/tfhe_hip.h)."""
+    _fields_ = [(k, C.c_uint32) for k in ("c_in", "h", "w", "c_out", "kh", "kw", "stride_h", "stride_w", "pad_h",
+                                          "pad_w", "groups")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 u64p = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")
 i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
 VP = C.c_void_p
@@ -148,6 +157,11 @@ _SIGS = {
     "tfhe_eval_dense_device": ([VP, SZ, SZ, VP, SZ, VP, VP, U64, VP, VP, VP], C.c_int),
     "tfhe_eval_dense": ([VP, SZ, SZ, u64p, SZ, i64p, VP, U64, u64p, u64p], C.c_int),
     "tfhe_mm_tiles": ([C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], None),
+    "tfhe_conv2d_shape": ([VP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(SZ)], C.c_int),
+    "tfhe_ciphertext_conv2d_device": ([VP, VP, SZ, VP, VP, VP, U64, VP, VP], C.c_int),
+    "tfhe_eval_conv2d_device": ([VP, VP, SZ, VP, VP, VP, U64, VP, VP, VP], C.c_int),
+    "tfhe_eval_conv2d": ([VP, VP, SZ, u64p, i64p, VP, U64, u64p, u64p], C.c_int),
+    "tfhe_conv2d_tiles": ([C.POINTER(C.c_int)] * 4, None),
     "tfhe_keygen_device": ([P, U64, C.c_int, VP, VP, VP, C.POINTER(U64), VP], C.c_int),
     "tfhe_setup_keygen": ([C.POINTER(VP), P, U64, C.c_int, u64p, C.POINTER(U64)], C.c_int),
     "tfhe_encrypt_device": ([P, C.c_int, VP, SZ, VP, U64, U64, U64, VP, C.POINTER(U64), VP], C.c_int),
@@ -246,6 +260,21 @@ def mm_tiles() -> tuple[int, int, int]:
     kt, ct, th = C.c_int(), C.c_int(), C.c_int()
     lib().tfhe_mm_tiles(C.byref(kt), C.byref(ct), C.byref(th))
     return kt.value, ct.value, th.value
+
+
+def conv2d_tiles() -> tuple[int, int, int, int]:
+    """(K-tile, output-plane tile, threads per workgroup, output positions per workgroup) of the convolution kernel
+    (tfhe_conv2d_tiles)."""
+    v = [C.c_int() for _ in range(4)]
+    lib().tfhe_conv2d_tiles(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def conv2d_shape(desc: Conv2d) -> tuple[int, int, int]:
+    """(oh, ow, K = (c_in / groups) kh kw) of a convolution; validates the descriptor (tfhe_conv2d_shape; no GPU)."""
+    oh, ow, K = C.c_uint32(), C.c_uint32(), SZ()
+    check(lib().tfhe_conv2d_shape(C.byref(desc), C.byref(oh), C.byref(ow), C.byref(K)), "tfhe_conv2d_shape")
+    return oh.value, ow.value, K.value
 
 
 def host_selftest(p: Params):

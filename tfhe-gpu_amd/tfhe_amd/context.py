@@ -9,7 +9,7 @@ from contextlib import contextmanager
 
 import numpy as np
 
-from .capi import BINGATE, Info, Knobs, Params, check, lib
+from .capi import BINGATE, Conv2d, Info, Knobs, Params, TfheError, check, conv2d_shape, lib
 
 
 _M64 = (1 << 64) - 1
@@ -409,6 +409,63 @@ class BinFHEContextHIP:
                                                               C.c_void_p(d_matrix), C.c_void_p(d_bias), modulus,
                                                               C.c_void_p(d_out), C.c_void_p(stream)),
                     "tfhe_ciphertext_mul_matrix_device")
+
+    # -- convolution layers: y = f(conv(x) + b), the gathered product then one shared-table EvalFunc --
+    def EvalConv2d(self, cts, weight, lut, bias=None, stride=1, padding=0, groups=1, q=None):
+        """cts[instances, C, H, W, n+1] mod q (or [C, H, W, n+1]: one instance), weight[C_out, C/groups, kh, kw] int64
+        (OIHW), lut[q], bias[C_out] or None; stride and padding an int or a pair (rows, columns)
+        -> [instances, C_out, oh, ow, n+1] (or [C_out, oh, ow, n+1]); host arrays staged through the first device."""
+        w, qq = self.params.n + 1, q or self.params.q
+        x = _u64(cts)
+        one = x.ndim == 4
+        if one:
+            x = x[None]
+        W = np.ascontiguousarray(weight, dtype=np.int64)
+        if W.ndim != 4 or 0 in W.shape:
+            raise ValueError(f"EvalConv2d: weight must be 4-D [C_out][C/groups][kh][kw] and not empty, got {W.shape}")
+        if x.ndim != 5 or 0 in x.shape or x.shape[4] != w:
+            raise ValueError(f"EvalConv2d: expected shape (instances, C, H, W, {w}), got {x.shape}")
+        sh, sw = (stride, stride) if np.isscalar(stride) else stride
+        ph, pw = (padding, padding) if np.isscalar(padding) else padding
+        if groups < 1 or x.shape[1] != W.shape[1] * groups:
+            raise ValueError(f"EvalConv2d: {x.shape[1]} input planes against weight {W.shape} with groups = {groups}")
+        if min(sh, sw) < 1 or min(ph, pw) < 0:
+            raise ValueError(f"EvalConv2d: stride {stride} must be >= 1 and padding {padding} >= 0")
+        desc = Conv2d(x.shape[1], x.shape[2], x.shape[3], W.shape[0], W.shape[2], W.shape[3], sh, sw, ph, pw, groups)
+        try:
+            oh, ow, _ = conv2d_shape(desc)  # the descriptor's own rules, on the host; the message names the field
+        except TfheError as e:
+            raise ValueError(f"EvalConv2d: {e}") from None
+        lut = _u64(lut)
+        if lut.shape != (qq,):
+            raise ValueError(f"EvalConv2d: LUT must have shape ({qq},), got {lut.shape}")
+        b = None
+        if bias is not None:
+            b = _u64(bias)
+            if b.shape != (W.shape[0],):
+                raise ValueError(f"EvalConv2d: bias must have shape ({W.shape[0]},), got {b.shape}")
+        x = np.ascontiguousarray(x)
+        out = np.empty((x.shape[0], W.shape[0], oh, ow, w), dtype=np.uint64)
+        self._check(self._L.tfhe_eval_conv2d(self._h, C.byref(desc), x.shape[0], x.ravel(), W.ravel(),
+                                             C.c_void_p(b.ctypes.data if b is not None else None), qq, lut, out.ravel()),
+                    "tfhe_eval_conv2d")
+        return out[0] if one else out
+
+    def EvalConv2dDevice(self, desc, instances, d_ct, d_weight, d_lut, d_out, d_bias=0, q=None, stream=0):
+        """desc: tfhe_amd.Conv2d; d_ct[instances][c_in][h][w][n+1], d_weight[c_out][c_in/groups][kh][kw] int64, d_lut[q],
+        d_bias[c_out] or 0 -> d_out[instances][c_out][oh][ow][n+1], device pointers."""
+        self._check(self._L.tfhe_eval_conv2d_device(self._h, C.byref(desc), instances, C.c_void_p(d_ct),
+                                                    C.c_void_p(d_weight), C.c_void_p(d_bias), q or self.params.q,
+                                                    C.c_void_p(d_lut), C.c_void_p(d_out), C.c_void_p(stream)),
+                    "tfhe_eval_conv2d_device")
+
+    def CiphertextConv2dDevice(self, desc, instances, d_ct, d_weight, modulus, d_out, d_bias=0, stream=0):
+        """The gathered product alone at any modulus: d_ct[instances][c_in][h][w][n+1], d_weight (OIHW int64, shared),
+        d_bias[c_out] or 0 -> d_out[instances][c_out][oh][ow][n+1]; no input is written."""
+        self._check(self._L.tfhe_ciphertext_conv2d_device(self._h, C.byref(desc), instances, C.c_void_p(d_ct),
+                                                          C.c_void_p(d_weight), C.c_void_p(d_bias), modulus,
+                                                          C.c_void_p(d_out), C.c_void_p(stream)),
+                    "tfhe_ciphertext_conv2d_device")
 
     # -- device-resident (pointers are integers, e.g. torch tensor.data_ptr()) --
     def EvalBinGateDevice(self, gate, B, d_ct1, d_ct2, d_out, q=None, stream=0):
