@@ -411,6 +411,48 @@ tfhe_status tfhe_eval_conv2d(tfhe_ctx* ctx, const tfhe_conv2d* d, size_t instanc
  * per workgroup (any pointer may be NULL) */
 void tfhe_conv2d_tiles(int* kt, int* ct, int* threads, int* positions);
 
+/* ---- pooling layers (no reference counterpart; new symbols only, the ABI version stays) ----
+ * A windowed pairwise reduction whose pair step is one EvalFunc: with a ReLU table it is max pooling.
+ * ct[instances][c][h][w][n+1] mod q -> out[instances][c][oh][ow][n+1], oh = (h + 2 pad_h - kh) / stride_h + 1 and ow
+ * likewise: the output layout is the input layout.  Every (instance, plane, oy, ox) is reduced on its own, every
+ * step on all n+1 words:
+ *   L0 = the window's taps inside [0, h) x [0, w), in order t = ky kw + kx (a tap in the padding is left out: the
+ *        -infinity padding of max_pool2d; pad < window leaves at least one);
+ *   round l: L_{l+1}[j] = op(L_l[2j], L_l[2j+1]) for every complete pair; an odd last element is carried unchanged
+ *        (no bootstrap, no copy); the reduction ends when one element is left;
+ *   op(a, b) = b + EvalFunc(a - b mod q, lut) mod q, EvalFunc being tfhe_eval_func with one shared table lut[q].
+ * The result equals that tournament composed on host arrays with tfhe_eval_func bit for bit.  All the pairs of a
+ * round, over every instance, plane and position, are one flat EvalFunc batch, run in slices beyond 65,536.  The
+ * table is classified as in tfhe_eval_dense_device (an arbitrary-class table with q > N is TFHE_ERR_UNSUPPORTED
+ * before anything is launched); tfhe_info.bootstraps grows by pairs c instances (1: negacyclic, 2: otherwise),
+ * pairs = sum over positions of (valid taps - 1).  A 1 x 1 window is a strided copy with no bootstrap.  No input
+ * word is written.  The descriptor's rules and messages are tfhe_conv2d's: no zero field, pad < window, window <=
+ * padded plane.  Argument errors -- a null pointer, instances = 0, q < 8, q not a power of two or not dividing 2N,
+ * a size product that overflows size_t -- are TFHE_ERR_INVALID_ARGUMENT, reported before any device call; a buffer
+ * on a device the context does not use is TFHE_ERR_INVALID_ARGUMENT as for the other _device calls. */
+typedef struct tfhe_pool2d {
+    uint32_t c, h, w;             /* planes and their size */
+    uint32_t kh, kw;              /* window */
+    uint32_t stride_h, stride_w;  /* >= 1 */
+    uint32_t pad_h, pad_w;        /* left-out rows / columns on each side: pad_h < kh, pad_w < kw */
+} tfhe_pool2d;
+
+/* host only, no GPU: validates the descriptor; oh, ow, the rounds of the longest tournament, pairs per plane (any
+ * pointer may be NULL) */
+tfhe_status tfhe_pool2d_shape(const tfhe_pool2d* d, uint32_t* oh, uint32_t* ow, uint32_t* rounds, size_t* pairs);
+/* host only, no GPU: the same tournament on clear values mod q (a power of two >= 8), in[instances][c][h][w] ->
+ * out[instances][c][oh][ow] with op(a, b) = b + lut[a - b mod q] mod q; mirrors tfhe_fcircuit_eval_plain */
+tfhe_status tfhe_pool2d_eval_plain(const tfhe_pool2d* d, size_t instances, uint64_t q, const uint64_t* lut,
+                                   const uint64_t* in, uint64_t* out);
+/* device = the one holding d_out; ordered on `stream`.  Uses the dense layer's grow-only store and a slot store
+ * of instances c slots (n+1) words for the results that are not outputs; the plan is uploaded once per
+ * (descriptor, device) and kept in the context */
+tfhe_status tfhe_eval_pool2d_device(tfhe_ctx* ctx, const tfhe_pool2d* d, size_t instances, const uint64_t* d_ct,
+                                    uint64_t q, const uint64_t* d_lut, uint64_t* d_out, void* stream);
+/* the same on host arrays, staged through the context's first device as tfhe_eval_conv2d */
+tfhe_status tfhe_eval_pool2d(tfhe_ctx* ctx, const tfhe_pool2d* d, size_t instances, const uint64_t* ct, uint64_t q,
+                             const uint64_t* lut, uint64_t* out);
+
 /* ---- key generation, encryption and decryption on the device (no reference counterpart; new symbols only, the
  * ABI version stays) ----
  * FOR TESTS, BENCHMARKS AND REPRODUCIBLE EXPERIMENTS.  The generator is splitmix64 from a 64-bit seed: it

@@ -162,7 +162,20 @@ struct Device {
     size_t mm_mat_words = 0;
     uint64_t* dense_z = nullptr;
     size_t dense_z_words = 0;
+    // The pooling layer's stores (dev_pool2d): the results that are not outputs, instances c slots (n+1) words,
+    // under the same rules; and the uploaded plans, one per descriptor, written once and freed only by hipFree
+    // (which waits for the kernels still reading them): at most kPoolPlans, the oldest evicted.
+    uint64_t* pool_slots = nullptr;
+    size_t pool_slots_words = 0;
+    struct PoolPlanDev {
+        PoolGeom g{};
+        PoolRec* recs = nullptr;          // device: the plan's records
+        std::vector<size_t> round_first;  // PoolPlan::round_first
+        size_t copies = 0, slots = 0, widest = 0;
+    };
+    std::vector<PoolPlanDev> pool_plans;
 };
+constexpr size_t kPoolPlans = 16;
 
 // hipMalloc'd buffer owned by one scope (error paths free it too)
 struct DevBuf {
@@ -476,6 +489,9 @@ void free_device(Device& d) {
     hipFree(d.wires);
     hipFree(d.mm_mat);
     hipFree(d.dense_z);
+    hipFree(d.pool_slots);
+    for (auto& pp : d.pool_plans) hipFree(pp.recs);
+    d.pool_plans.clear();
     hipFree(d.duo.base);
     if (d.duo.fence) hipEventDestroy(d.duo.fence);
     delete d.duo.mu;
@@ -837,6 +853,42 @@ tfhe_status dev_conv_layer(tfhe_ctx* c, Device& d, int prop, const ConvGeom& g, 
     for (size_t first = 0; first < total; first += slice) {
         const size_t B = std::min(slice, total - first);
         SCHECK(dev_func(c, d, prop, d.dense_z + first * w, q, d_lut, 0, out + first * w, B));
+    }
+    return TFHE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the pooling layer on one device (inside run_device_op)
+// ---------------------------------------------------------------------------
+// Round by round: the round's pairs over every instance and plane are one flat batch, item = plane nrec + record;
+// per slice of the scratch, z = a - b into the first half of d.dense_z, EvalFunc into the second, dst = f + b into
+// d.pool_slots or out.  A round reads inputs and earlier rounds' slots and writes fresh slots and outputs, so
+// its slices are independent.  Positions with one valid tap are copied.
+tfhe_status dev_pool2d(tfhe_ctx* c, Device& d, int prop, const Device::PoolPlanDev& pp, size_t instances,
+                       const uint64_t* ct, uint64_t q, const uint64_t* d_lut, uint64_t* out) {
+    const PoolGeom& g = pp.g;
+    const size_t w = c->p.n + 1, planes = instances * g.c, slice = std::min(d.sc.cap, c->max_chunk);
+    PoolArgs a{};
+    a.width = (uint32_t)w, a.mask = q - 1;
+    a.in = ct, a.in_plane = (size_t)g.h * g.w * w;
+    a.slots = d.pool_slots, a.slot_plane = pp.slots * w;
+    a.out = out, a.out_plane = (size_t)g.oh * g.ow * w;
+    uint64_t *z = d.dense_z, *f = d.dense_z + std::min(planes * pp.widest, c->max_chunk) * w;
+    for (size_t l = 0; l + 1 < pp.round_first.size(); ++l) {
+        a.recs = pp.recs + pp.round_first[l];
+        a.nrec = pp.round_first[l + 1] - pp.round_first[l];
+        const size_t total = planes * a.nrec;
+        for (a.first = 0; a.first < total; a.first += slice) {
+            a.count = std::min(slice, total - a.first);
+            HCHECK(launch_pool_diff(a, z, d.stream));
+            SCHECK(dev_func(c, d, prop, z, q, d_lut, 0, f, a.count));
+            HCHECK(launch_pool_add(a, f, d.stream));
+        }
+    }
+    if (pp.copies) {
+        a.recs = pp.recs + pp.round_first.back();
+        a.nrec = pp.copies, a.first = 0, a.count = planes * pp.copies;
+        HCHECK(launch_pool_copy(a, d.stream));
     }
     return TFHE_OK;
 }
@@ -2832,13 +2884,17 @@ void tfhe_mm_tiles(int* kt, int* ct, int* threads) {
 extern "C++" {
 namespace {
 // the descriptor's own rules (no context, no device): every message names the field
-tfhe_status conv_geometry(const tfhe_conv2d* d, ConvGeom& g, size_t& K) {
-    const auto bad = [](const std::string& what) { return fail(TFHE_ERR_INVALID_ARGUMENT, "Conv2d: " + what); };
+// (the pooling descriptor passes through here as a depthwise convolution: `who` and the name of its planes field)
+tfhe_status conv_geometry(const tfhe_conv2d* d, ConvGeom& g, size_t& K, const char* who = "Conv2d",
+                          const char* planes = "c_in") {
+    const auto bad = [who](const std::string& what) {
+        return fail(TFHE_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what);
+    };
     if (!d) return bad("null descriptor");
     const struct {
         uint32_t v;
         const char* name;
-    } nonzero[] = {{d->c_in, "c_in"}, {d->h, "h"}, {d->w, "w"}, {d->c_out, "c_out"}, {d->kh, "kh"}, {d->kw, "kw"},
+    } nonzero[] = {{d->c_in, planes}, {d->h, "h"}, {d->w, "w"}, {d->c_out, "c_out"}, {d->kh, "kh"}, {d->kw, "kw"},
                    {d->stride_h, "stride_h"}, {d->stride_w, "stride_w"}, {d->groups, "groups"}};
     for (const auto& f : nonzero)
         if (f.v == 0) return bad(std::string(f.name) + " is 0");
@@ -2998,6 +3054,161 @@ void tfhe_conv2d_tiles(int* kt, int* ct, int* threads, int* positions) {
     if (ct) *ct = CV_CT;
     if (threads) *threads = CV_THREADS;
     if (positions) *positions = CV_P;
+}
+
+extern "C++" {
+namespace {
+// the descriptor's rules are the convolution's, by the convolution's code: a pooling window is a depthwise one
+tfhe_status pool_geometry(const tfhe_pool2d* d, PoolGeom& g, uint32_t& rounds, size_t& pairs) {
+    if (!d) return fail(TFHE_ERR_INVALID_ARGUMENT, "Pool2d: null descriptor");
+    const tfhe_conv2d cd{d->c, d->h, d->w, d->c, d->kh, d->kw, d->stride_h, d->stride_w, d->pad_h, d->pad_w, d->c};
+    ConvGeom cg;
+    size_t K = 0;
+    SCHECK(conv_geometry(&cd, cg, K, "Pool2d", "c"));
+    g = PoolGeom{d->c, d->h, d->w, d->kh, d->kw, d->stride_h, d->stride_w, d->pad_h, d->pad_w, cg.oh, cg.ow};
+    if (!pool_counts(g, rounds, pairs)) return fail(TFHE_ERR_INVALID_ARGUMENT, "Pool2d: sizes overflow");
+    return TFHE_OK;
+}
+
+// what the pooling calls check before any device call (N = 0: no context, q need only be a power of two >= 8);
+// `words` is n+1, or 1 for clear values
+tfhe_status check_pool_args(const char* who, const tfhe_pool2d* desc, size_t instances, const void* in, uint64_t q,
+                            uint64_t N, const void* lut, const void* out, size_t words, PoolGeom& g, size_t& pairs) {
+    const auto bad = [who](const std::string& what) {
+        return fail(TFHE_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what);
+    };
+    if (!desc) return bad("null descriptor");
+    if (!in) return bad("null ct");
+    if (!lut) return bad("null lut");
+    if (!out) return bad("null out");
+    if (instances == 0) return bad("instances is 0");
+    uint32_t rounds = 0;
+    SCHECK(pool_geometry(desc, g, rounds, pairs));
+    if (q < 8 || (q & (q - 1)) != 0 || (N && (2ull * N) % q != 0))
+        return bad(N ? "q must be a power of two >= 8 that divides 2N" : "q must be a power of two >= 8");
+    size_t src = sizeof(uint64_t), res = sizeof(uint64_t), mid = sizeof(PoolRec);
+    // inputs, outputs, and what the pairs can need at most: a record each; a slot and two flat rows each
+    const bool ok = conv_mul(src, instances) && conv_mul(src, g.c) && conv_mul(src, g.h) && conv_mul(src, g.w) &&
+                    conv_mul(src, words) && conv_mul(res, instances) && conv_mul(res, g.c) && conv_mul(res, g.oh) &&
+                    conv_mul(res, g.ow) && conv_mul(res, words) && conv_mul(mid, instances) && conv_mul(mid, g.c) &&
+                    conv_mul(mid, pairs ? pairs : 1) && conv_mul(mid, words);
+    if (!ok) return bad("sizes overflow");
+    return TFHE_OK;
+}
+
+// the device copy of the plan of `g`: built and uploaded on first use, then kept
+tfhe_status pool_plan_on_device(Device& d, const PoolGeom& g, const Device::PoolPlanDev*& out) {
+    for (const auto& pp : d.pool_plans)
+        if (std::memcmp(&pp.g, &g, sizeof g) == 0) {
+            out = &pp;
+            return TFHE_OK;
+        }
+    const PoolPlan plan = pool_plan(g);
+    Device::PoolPlanDev pp;
+    pp.g = g, pp.round_first = plan.round_first, pp.copies = plan.copies, pp.slots = plan.slots;
+    pp.widest = plan.widest();
+    if (!plan.recs.empty()) {
+        HCHECK(hipMalloc(&pp.recs, plan.recs.size() * sizeof(PoolRec)));
+        const hipError_t e = hipMemcpy(pp.recs, plan.recs.data(), plan.recs.size() * sizeof(PoolRec), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            hipFree(pp.recs);
+            HCHECK(e);
+        }
+    }
+    if (d.pool_plans.size() >= kPoolPlans) {
+        hipFree(d.pool_plans.front().recs);  // waits for the kernels still reading it
+        d.pool_plans.erase(d.pool_plans.begin());
+    }
+    d.pool_plans.push_back(std::move(pp));
+    out = &d.pool_plans.back();
+    return TFHE_OK;
+}
+
+// d_out selects the device; the table's class comes from its first q words, read back once
+tfhe_status pool_on_device(tfhe_ctx* c, const PoolGeom& g, size_t instances, const uint64_t* d_ct, uint64_t q,
+                           const uint64_t* d_lut, uint64_t* d_out, void* stream) {
+    Device* dp = nullptr;
+    SCHECK(device_for(c, d_out, dp));
+    HCHECK(hipSetDevice(dp->id));
+    std::vector<uint64_t> lut0(q);
+    hipStream_t s = stream ? (hipStream_t)stream : dp->stream;
+    HCHECK(hipMemcpyAsync(lut0.data(), d_lut, q * 8, hipMemcpyDeviceToHost, s));
+    HCHECK(hipStreamSynchronize(s));
+    const int prop = check_input_function(lut0.data(), q, q);
+    if (prop == 2 && q > c->p.N) return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
+    const Device::PoolPlanDev* pp = nullptr;
+    SCHECK(pool_plan_on_device(*dp, g, pp));
+    const size_t w = c->p.n + 1, planes = instances * g.c, B = std::min(planes * pp->widest, c->max_chunk);
+    SCHECK(ensure_words(*dp, dp->dense_z, dp->dense_z_words, 2 * B * w));
+    SCHECK(ensure_words(*dp, dp->pool_slots, dp->pool_slots_words, planes * pp->slots * w));
+    return run_device_op(c, B, d_out, stream, [&](Device& d) {
+        return dev_pool2d(c, d, prop, *pp, instances, d_ct, q, d_lut, d_out);
+    });
+}
+}  // namespace
+}  // extern "C++"
+
+tfhe_status tfhe_pool2d_shape(const tfhe_pool2d* d, uint32_t* oh, uint32_t* ow, uint32_t* rounds, size_t* pairs) {
+    return guarded([&]() -> tfhe_status {
+        PoolGeom g;
+        uint32_t r = 0;
+        size_t p = 0;
+        SCHECK(pool_geometry(d, g, r, p));
+        if (oh) *oh = g.oh;
+        if (ow) *ow = g.ow;
+        if (rounds) *rounds = r;
+        if (pairs) *pairs = p;
+        return TFHE_OK;
+    });
+}
+
+tfhe_status tfhe_pool2d_eval_plain(const tfhe_pool2d* desc, size_t instances, uint64_t q, const uint64_t* lut,
+                                   const uint64_t* in, uint64_t* out) {
+    return guarded([&]() -> tfhe_status {
+        PoolGeom g;
+        size_t pairs = 0;
+        SCHECK(check_pool_args("Pool2dEvalPlain", desc, instances, in, q, 0, lut, out, 1, g, pairs));
+        pool_eval_plain(g, pool_plan(g), instances, q, lut, in, out);
+        return TFHE_OK;
+    });
+}
+
+tfhe_status tfhe_eval_pool2d_device(tfhe_ctx* c, const tfhe_pool2d* desc, size_t instances, const uint64_t* d_ct,
+                                    uint64_t q, const uint64_t* d_lut, uint64_t* d_out, void* stream) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_ctx(c));
+        PoolGeom g;
+        size_t pairs = 0;
+        SCHECK(check_pool_args("EvalPool2d", desc, instances, d_ct, q, c->p.N, d_lut, d_out, c->p.n + 1, g, pairs));
+        return pool_on_device(c, g, instances, d_ct, q, d_lut, d_out, stream);
+    });
+}
+
+tfhe_status tfhe_eval_pool2d(tfhe_ctx* c, const tfhe_pool2d* desc, size_t instances, const uint64_t* ct, uint64_t q,
+                             const uint64_t* lut, uint64_t* out) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_ctx(c));
+        PoolGeom g;
+        size_t pairs = 0;
+        SCHECK(check_pool_args("EvalPool2d", desc, instances, ct, q, c->p.N, lut, out, c->p.n + 1, g, pairs));
+        // the class is known from the host table: refuse before anything is allocated or launched
+        if (check_input_function(lut, q, q) == 2 && q > c->p.N)
+            return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
+        Device& d = c->devs[0];
+        HCHECK(hipSetDevice(d.id));
+        const size_t w = c->p.n + 1, wi = instances * g.c * g.h * g.w * w, wo = instances * g.c * g.oh * g.ow * w;
+        // one block: ct | lut | out
+        DevBuf buf;
+        HCHECK(hipMalloc(&buf.p, (wi + q + wo) * sizeof(uint64_t)));
+        uint64_t *dct = buf.as<uint64_t>(), *dl = dct + wi, *dout = dl + q;
+        tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wi, d.stream);
+        if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(lut, q), q, d.stream);
+        if (st == TFHE_OK) st = pool_on_device(c, g, instances, dct, q, dl, dout, nullptr);
+        if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
+        const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
+        if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalPool2d: ") + hipGetErrorString(e));
+        return st;
+    });
 }
 
 // GPULWEOperation::GPUSetup(numGPUs) (lwe-operation.cu:143-146) ignores numGPUs and works on device 0;

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "pool.hpp"
+
 namespace tfhe {
 
 // Scalar parameters every blind-rotation kernel needs (the reference's
@@ -308,5 +310,28 @@ struct ConvGeom {
 hipError_t launch_conv2d(uint32_t width, const ConvGeom& g, size_t instances, const uint64_t* ct,
                          const int64_t* weight, const uint64_t* bias, uint64_t modulus, uint64_t* mat_scratch,
                          uint64_t* out, hipStream_t s);
+
+// The windowed pairwise reduction's streaming kernels (pool2d.hip), around each round's EvalFunc.
+// Items [first, first + count) of a round's flat batch, item = (instance c + plane) nrec + r over the nrec
+// records of one plane (pool.hpp): launch_pool_diff writes z[it] = a - b mod q, launch_pool_add writes
+// dst = f[it] + b mod q, launch_pool_copy dst = b, it = item - first.  in [planes][in_plane words] is only read;
+// slots [planes][slot_plane] and out [planes][out_plane] are the destinations; mask = q - 1.  A workgroup of
+// PL_THREADS threads takes PL_ITEMS items at a time, one per wave.
+constexpr int PL_THREADS = 256, PL_ITEMS = PL_THREADS / 64;
+struct PoolArgs {
+    const PoolRec* recs;
+    size_t nrec, first, count;
+    uint32_t width;
+    uint64_t mask;
+    const uint64_t* in;
+    size_t in_plane;
+    uint64_t* slots;
+    size_t slot_plane;
+    uint64_t* out;
+    size_t out_plane;
+};
+hipError_t launch_pool_diff(const PoolArgs& p, uint64_t* z, hipStream_t s);
+hipError_t launch_pool_add(const PoolArgs& p, const uint64_t* f, hipStream_t s);
+hipError_t launch_pool_copy(const PoolArgs& p, hipStream_t s);
 
 }  // namespace tfhe

@@ -98,6 +98,14 @@ class Conv2d(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Pool2d(C.Structure):
+    """tfhe_pool2d: the geometry of a pooling window (include/tfhe_hip.h)."""
+    _fields_ = [(k, C.c_uint32) for k in ("c", "h", "w", "kh", "kw", "stride_h", "stride_w", "pad_h", "pad_w")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 u64p = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")
 i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
 VP = C.c_void_p
@@ -162,6 +170,10 @@ _SIGS = {
     "tfhe_eval_conv2d_device": ([VP, VP, SZ, VP, VP, VP, U64, VP, VP, VP], C.c_int),
     "tfhe_eval_conv2d": ([VP, VP, SZ, u64p, i64p, VP, U64, u64p, u64p], C.c_int),
     "tfhe_conv2d_tiles": ([C.POINTER(C.c_int)] * 4, None),
+    "tfhe_pool2d_shape": ([VP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(SZ)], C.c_int),
+    "tfhe_pool2d_eval_plain": ([VP, SZ, U64, VP, VP, VP], C.c_int),
+    "tfhe_eval_pool2d_device": ([VP, VP, SZ, VP, U64, VP, VP, VP], C.c_int),
+    "tfhe_eval_pool2d": ([VP, VP, SZ, u64p, U64, u64p, u64p], C.c_int),
     "tfhe_keygen_device": ([P, U64, C.c_int, VP, VP, VP, C.POINTER(U64), VP], C.c_int),
     "tfhe_setup_keygen": ([C.POINTER(VP), P, U64, C.c_int, u64p, C.POINTER(U64)], C.c_int),
     "tfhe_encrypt_device": ([P, C.c_int, VP, SZ, VP, U64, U64, U64, VP, C.POINTER(U64), VP], C.c_int),
@@ -275,6 +287,61 @@ def conv2d_shape(desc: Conv2d) -> tuple[int, int, int]:
     oh, ow, K = C.c_uint32(), C.c_uint32(), SZ()
     check(lib().tfhe_conv2d_shape(C.byref(desc), C.byref(oh), C.byref(ow), C.byref(K)), "tfhe_conv2d_shape")
     return oh.value, ow.value, K.value
+
+
+def pool2d_shape(desc: Pool2d) -> tuple[int, int, int, int]:
+    """(oh, ow, rounds of the longest tournament, pairs per plane) of a pooling window; validates the descriptor
+    (tfhe_pool2d_shape; no GPU)."""
+    oh, ow, rounds, pairs = C.c_uint32(), C.c_uint32(), C.c_uint32(), SZ()
+    check(lib().tfhe_pool2d_shape(C.byref(desc), C.byref(oh), C.byref(ow), C.byref(rounds), C.byref(pairs)),
+          "tfhe_pool2d_shape")
+    return oh.value, ow.value, rounds.value, pairs.value
+
+
+def pool2d_eval_plain(desc: Pool2d, values, lut, q: int):
+    """The pooling tournament on clear values mod q: values[instances, c, h, w] (or [c, h, w]) and lut[q] ->
+    [instances, c, oh, ow], op(a, b) = b + lut[a - b mod q] mod q (tfhe_pool2d_eval_plain; no GPU)."""
+    x = np.ascontiguousarray(values, dtype=np.uint64)
+    one = x.ndim == 3
+    if one:
+        x = x[None]
+    if x.ndim != 4 or x.shape[1:] != (desc.c, desc.h, desc.w):
+        raise ValueError(f"pool2d_eval_plain: expected shape (instances, {desc.c}, {desc.h}, {desc.w}), got {x.shape}")
+    lut = np.ascontiguousarray(lut, dtype=np.uint64)
+    if lut.shape != (q,):
+        raise ValueError(f"pool2d_eval_plain: LUT must have shape ({q},), got {lut.shape}")
+    oh, ow, _, _ = pool2d_shape(desc)
+    x = np.ascontiguousarray(x)
+    out = np.empty((x.shape[0], desc.c, oh, ow), dtype=np.uint64)
+    check(lib().tfhe_pool2d_eval_plain(C.byref(desc), x.shape[0], q, C.c_void_p(lut.ctypes.data),
+                                       C.c_void_p(x.ctypes.data), C.c_void_p(out.ctypes.data)),
+          "tfhe_pool2d_eval_plain")
+    return out[0] if one else out
+
+
+def max_table(q: int, negacyclic: bool = False):
+    """The table that makes the pooling step op(a, b) = b + EvalFunc(a - b) a maximum: ReLU of the signed difference.
+
+    Default (arbitrary class, two bootstraps per pair): lut[x] = x for x < q/2, else 0; exact for differences in
+    (-q/2, q/2).
+
+    negacyclic=True (one bootstrap per pair), for inputs whose differences stay inside (-q/4, q/4), one more bit of
+    headroom: lut[x] = x on [0, q/4), 0 on [q/4, q/2), and the upper half mirrored, lut[x + q/2] = q - lut[x].
+    checkInputFunction compares lut[i] with q - lut[i + q/2], so a zero entry can never pass as negacyclic: the
+    helper writes 1 for those zeros (lut[0] and [q/4, q/2)) and q - 1 for their mirrors.  A pair step then returns
+    max(a, b) + 1 where a = b, max(a, b) - 1 where a < b and max(a, b) where a > b: one unit of the noise bits.
+
+    On ciphertexts EvalFunc looks a table up at phase + beta (beta = 128), so under either table a pair step whose
+    first operand wins or ties returns it beta higher: choose p with q / 2p above 128 per round plus the noise
+    (DESIGN 3.11)."""
+    if q < 8 or q & (q - 1):
+        raise ValueError(f"max_table: q must be a power of two >= 8, got {q}")
+    x = np.arange(q, dtype=np.uint64)
+    if not negacyclic:
+        return np.where(x < q // 2, x, 0).astype(np.uint64)
+    half = np.where(x[:q // 2] < q // 4, x[:q // 2], 0)
+    half[half == 0] = 1
+    return np.concatenate([half, q - half]).astype(np.uint64)
 
 
 def host_selftest(p: Params):

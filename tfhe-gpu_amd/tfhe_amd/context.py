@@ -9,7 +9,8 @@ from contextlib import contextmanager
 
 import numpy as np
 
-from .capi import BINGATE, Conv2d, Info, Knobs, Params, TfheError, check, conv2d_shape, lib
+from .capi import (BINGATE, Conv2d, Info, Knobs, Params, Pool2d, TfheError, check, conv2d_shape, lib, max_table,
+                   pool2d_shape)
 
 
 _M64 = (1 << 64) - 1
@@ -466,6 +467,51 @@ class BinFHEContextHIP:
                                                           C.c_void_p(d_weight), C.c_void_p(d_bias), modulus,
                                                           C.c_void_p(d_out), C.c_void_p(stream)),
                     "tfhe_ciphertext_conv2d_device")
+
+    # -- pooling layers: a windowed pair tournament, op(a, b) = b + EvalFunc(a - b) with one shared table --
+    def EvalPool2d(self, cts, lut, kernel, stride=None, padding=0, q=None):
+        """cts[instances, C, H, W, n+1] mod q (or [C, H, W, n+1]: one instance), lut[q]; kernel, stride and padding an
+        int or a pair (rows, columns), stride defaulting to the kernel as in PyTorch -> [instances, C, oh, ow, n+1]
+        (or [C, oh, ow, n+1]); host arrays staged through the first device.  With tfhe_amd.max_table(q) it is max
+        pooling (EvalMaxPool2d); a tap in the padding is left out."""
+        w, qq = self.params.n + 1, q or self.params.q
+        x = _u64(cts)
+        one = x.ndim == 4
+        if one:
+            x = x[None]
+        if x.ndim != 5 or 0 in x.shape or x.shape[4] != w:
+            raise ValueError(f"EvalPool2d: expected shape (instances, C, H, W, {w}), got {x.shape}")
+        kh, kw = (kernel, kernel) if np.isscalar(kernel) else kernel
+        sh, sw = (kh, kw) if stride is None else (stride, stride) if np.isscalar(stride) else stride
+        ph, pw = (padding, padding) if np.isscalar(padding) else padding
+        if min(kh, kw, sh, sw) < 1 or min(ph, pw) < 0:
+            raise ValueError(f"EvalPool2d: kernel {kernel} and stride {stride} must be >= 1 and padding {padding} >= 0")
+        desc = Pool2d(x.shape[1], x.shape[2], x.shape[3], kh, kw, sh, sw, ph, pw)
+        try:
+            oh, ow, _, _ = pool2d_shape(desc)  # the descriptor's own rules, on the host; the message names the field
+        except TfheError as e:
+            raise ValueError(f"EvalPool2d: {e}") from None
+        lut = _u64(lut)
+        if lut.shape != (qq,):
+            raise ValueError(f"EvalPool2d: LUT must have shape ({qq},), got {lut.shape}")
+        x = np.ascontiguousarray(x)
+        out = np.empty((x.shape[0], x.shape[1], oh, ow, w), dtype=np.uint64)
+        self._check(self._L.tfhe_eval_pool2d(self._h, C.byref(desc), x.shape[0], x.ravel(), qq, lut, out.ravel()),
+                    "tfhe_eval_pool2d")
+        return out[0] if one else out
+
+    def EvalMaxPool2d(self, cts, kernel, stride=None, padding=0, negacyclic=False, q=None):
+        """Max pooling: EvalPool2d with tfhe_amd.max_table(q, negacyclic).  The default table takes two bootstraps per
+        pair and differences in (-q/2, q/2); negacyclic=True takes one and differences in (-q/4, q/4)."""
+        return self.EvalPool2d(cts, max_table(q or self.params.q, negacyclic), kernel, stride, padding, q)
+
+    def EvalPool2dDevice(self, desc, instances, d_ct, d_lut, d_out, q=None, stream=0):
+        """desc: tfhe_amd.Pool2d; d_ct[instances][c][h][w][n+1], d_lut[q] -> d_out[instances][c][oh][ow][n+1], device
+        pointers; no input word is written."""
+        self._check(self._L.tfhe_eval_pool2d_device(self._h, C.byref(desc), instances, C.c_void_p(d_ct),
+                                                    q or self.params.q, C.c_void_p(d_lut), C.c_void_p(d_out),
+                                                    C.c_void_p(stream)),
+                    "tfhe_eval_pool2d_device")
 
     # -- device-resident (pointers are integers, e.g. torch tensor.data_ptr()) --
     def EvalBinGateDevice(self, gate, B, d_ct1, d_ct2, d_out, q=None, stream=0):
