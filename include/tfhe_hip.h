@@ -453,6 +453,55 @@ tfhe_status tfhe_eval_pool2d_device(tfhe_ctx* ctx, const tfhe_pool2d* d, size_t 
 tfhe_status tfhe_eval_pool2d(tfhe_ctx* ctx, const tfhe_pool2d* d, size_t instances, const uint64_t* ct, uint64_t q,
                              const uint64_t* lut, uint64_t* out);
 
+/* ---- one table per channel: EvalFunc and the three layers (no reference counterpart; new symbols only, the ABI
+ * version stays) ----
+ * THE RULE.  A call takes luts[num_luts][q] and inner >= 1; ciphertext i of the flat batch uses table
+ * t(i) = (i / inner) mod num_luts, i the index in the whole batch.  Every table is classified on its own by the
+ * reference's checkInputFunction (as tfhe_fcircuit_compile does; not from the first table, as per_ct_lut does), and
+ * the result for ciphertext i equals tfhe_eval_func with the shared table luts[t(i)] on that ciphertext, bit for
+ * bit, whatever mixture of classes the batch holds.  tfhe_info.bootstraps grows by 1 per ciphertext on a
+ * negacyclic table and 2 per ciphertext on any other.  If any table is of the arbitrary class and q > N the call
+ * is TFHE_ERR_UNSUPPORTED before anything is launched and the counter does not move.  num_luts = 1 is the
+ * shared-table result.  No input is written; d_out must not overlap an input.  The device forms read the
+ * num_luts q table words back once per call.  The layers use the rule on their flat result
+ * [instances][channels][positions]: dense inner = 1, num_luts = cols; convolution inner = oh ow, num_luts = c_out;
+ * pooling one table per plane, num_luts = c, in every round.  The host forms stage through the context's first
+ * device; a tabled batch is not sharded over devices.
+ * Errors before any device call, TFHE_ERR_INVALID_ARGUMENT with a message naming the field: a null pointer; B,
+ * num_luts or inner = 0; q < 8, q not a power of two or q not dividing 2N; a size product that overflows; for the
+ * layers, num_luts other than the channel count (and the layer's own rules). */
+/* host only, no GPU (q need only be a power of two >= 8): classes[t] in {0 negacyclic, 1 periodic, 2 arbitrary}
+ * (may be NULL); per_class[3] = ciphertexts of a batch of B under (inner, num_luts) in each class; *bootstraps =
+ * what the call adds to tfhe_info.bootstraps */
+tfhe_status tfhe_lut_tables_info(uint64_t q, const uint64_t* luts, size_t num_luts, size_t inner, size_t B,
+                                 uint8_t* classes, size_t per_class[3], uint64_t* bootstraps);
+/* device = the one holding d_out; ordered on `stream`; sliced internally at the scratch capacity */
+tfhe_status tfhe_eval_func_tables_device(tfhe_ctx* ctx, size_t B, const uint64_t* d_ct, uint64_t q,
+                                         const uint64_t* d_luts, size_t num_luts, size_t inner, uint64_t* d_out,
+                                         void* stream);
+tfhe_status tfhe_eval_func_tables(tfhe_ctx* ctx, size_t B, const uint64_t* ct, uint64_t q, const uint64_t* luts,
+                                  size_t num_luts, size_t inner, uint64_t* out);
+/* as tfhe_eval_dense_device / tfhe_eval_dense with d_luts[cols][q] */
+tfhe_status tfhe_eval_dense_tables_device(tfhe_ctx* ctx, size_t instances, size_t K, const uint64_t* d_ct, size_t cols,
+                                          const int64_t* d_matrix, const uint64_t* d_bias, uint64_t q,
+                                          const uint64_t* d_luts, size_t num_luts, uint64_t* d_out, void* stream);
+tfhe_status tfhe_eval_dense_tables(tfhe_ctx* ctx, size_t instances, size_t K, const uint64_t* ct, size_t cols,
+                                   const int64_t* matrix, const uint64_t* bias, uint64_t q, const uint64_t* luts,
+                                   size_t num_luts, uint64_t* out);
+/* as tfhe_eval_conv2d_device / tfhe_eval_conv2d with d_luts[c_out][q] */
+tfhe_status tfhe_eval_conv2d_tables_device(tfhe_ctx* ctx, const tfhe_conv2d* d, size_t instances, const uint64_t* d_ct,
+                                           const int64_t* d_weight, const uint64_t* d_bias, uint64_t q,
+                                           const uint64_t* d_luts, size_t num_luts, uint64_t* d_out, void* stream);
+tfhe_status tfhe_eval_conv2d_tables(tfhe_ctx* ctx, const tfhe_conv2d* d, size_t instances, const uint64_t* ct,
+                                    const int64_t* weight, const uint64_t* bias, uint64_t q, const uint64_t* luts,
+                                    size_t num_luts, uint64_t* out);
+/* as tfhe_eval_pool2d_device / tfhe_eval_pool2d with d_luts[c][q] */
+tfhe_status tfhe_eval_pool2d_tables_device(tfhe_ctx* ctx, const tfhe_pool2d* d, size_t instances, const uint64_t* d_ct,
+                                           uint64_t q, const uint64_t* d_luts, size_t num_luts, uint64_t* d_out,
+                                           void* stream);
+tfhe_status tfhe_eval_pool2d_tables(tfhe_ctx* ctx, const tfhe_pool2d* d, size_t instances, const uint64_t* ct,
+                                    uint64_t q, const uint64_t* luts, size_t num_luts, uint64_t* out);
+
 /* ---- key generation, encryption and decryption on the device (no reference counterpart; new symbols only, the
  * ABI version stays) ----
  * FOR TESTS, BENCHMARKS AND REPRODUCIBLE EXPERIMENTS.  The generator is splitmix64 from a 64-bit seed: it

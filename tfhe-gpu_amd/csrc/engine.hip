@@ -174,6 +174,10 @@ struct Device {
         size_t copies = 0, slots = 0, widest = 0;
     };
     std::vector<PoolPlanDev> pool_plans;
+    // The class table of a call with one table per channel (dev_func_tables): 2 words per table, under the wire
+    // store's rules, written only when the call's tables are of more than one class.
+    uint64_t* tab_meta = nullptr;
+    size_t tab_meta_words = 0;
 };
 constexpr size_t kPoolPlans = 16;
 
@@ -490,6 +494,7 @@ void free_device(Device& d) {
     hipFree(d.mm_mat);
     hipFree(d.dense_z);
     hipFree(d.pool_slots);
+    hipFree(d.tab_meta);
     for (auto& pp : d.pool_plans) hipFree(pp.recs);
     d.pool_plans.clear();
     hipFree(d.duo.base);
@@ -654,14 +659,16 @@ tfhe_status dev_mkm(tfhe_ctx* c, Device& d, const uint64_t* ext, uint64_t fmod, 
 }
 
 // BootstrapFunc / BootstrapGate on device: ct[B][n+1] mod tv.ctmod -> out mod fmod
+// sel: the table modes read tv.lut[T][q] through it (one table per channel, dev_func_tables)
 tfhe_status dev_bootstrap(tfhe_ctx* c, Device& d, TvParams tv, uint64_t b_add, const uint64_t* ct, uint64_t* out,
-                          size_t B) {
+                          size_t B, const TabSel* sel = nullptr) {
     tv.N = c->p.N;
     tv.n = c->p.n;
     tv.Q = c->p.Q;
     tv.Q8 = c->p.Q / 8 + 1;
     if ((2ull * c->p.N) % tv.ctmod != 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "ciphertext modulus must divide 2N");
-    HCHECK(launch_build_testvector(tv, ct, d.sc.acc, d.sc.a, B, d.stream));
+    if (sel && tv.mode != TV_HALF) HCHECK(launch_build_testvector_tab(tv, *sel, ct, d.sc.acc, d.sc.a, B, d.stream));
+    else HCHECK(launch_build_testvector(tv, ct, d.sc.acc, d.sc.a, B, d.stream));
     SCHECK(dev_blind_rotate(c, d, d.sc.a, tv.ctmod, d.sc.acc, B));
     HCHECK(launch_extract(c->p.N, c->p.Q, b_add, d.sc.acc, d.sc.ext, B, d.stream));
     return dev_mkm(c, d, d.sc.ext, tv.fmod, out, B);
@@ -699,9 +706,10 @@ tfhe_status dev_gate(tfhe_ctx* c, Device& d, int gate, const uint64_t* ct1, cons
     return dev_bootstrap(c, d, tv, c->p.Q / 8 + 1, prep, out, B);
 }
 
-// vector EvalFunc, binfhe-base-scheme.cpp:679-924.  d_lut is a device LUT ([q] or [B][q]).
+// vector EvalFunc, binfhe-base-scheme.cpp:679-924.  d_lut is a device LUT ([q] or [B][q]); with sel, [T][q] of
+// class `prop` wherever sel points.
 tfhe_status dev_func(tfhe_ctx* c, Device& d, int prop, const uint64_t* ct, uint64_t q, const uint64_t* d_lut,
-                     uint64_t lut_stride, uint64_t* out, size_t B) {
+                     uint64_t lut_stride, uint64_t* out, size_t B, const TabSel* sel = nullptr) {
     const uint32_t n = c->p.n;
     const uint64_t beta = 128;
     hipStream_t s = d.stream;
@@ -715,7 +723,7 @@ tfhe_status dev_func(tfhe_ctx* c, Device& d, int prop, const uint64_t* ct, uint6
         tv.mode = TV_LUT;
         tv.ctmod = q;
         tv.fmod = q;
-        return dev_bootstrap(c, d, tv, 0, ct1, out, B);
+        return dev_bootstrap(c, d, tv, 0, ct1, out, B, sel);
     }
     if (prop == 2) {  // arbitrary: raise to 2q, two bootstraps
         if (q > c->p.N) return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
@@ -729,7 +737,7 @@ tfhe_status dev_func(tfhe_ctx* c, Device& d, int prop, const uint64_t* ct, uint6
         HCHECK(launch_lwe_op(LWE_ADD_CONST, n, dq, beta, ct3, nullptr, ct3, B, s));
         HCHECK(launch_lwe_op(LWE_SUB_CONST, n, dq, q >> 1, ct3, nullptr, ct3, B, s));
         tv.mode = TV_LUT2;
-        SCHECK(dev_bootstrap(c, d, tv, 0, ct3, out, B));
+        SCHECK(dev_bootstrap(c, d, tv, 0, ct3, out, B, sel));
         HCHECK(launch_lwe_op(LWE_SET_MOD, n, q, 0, out, nullptr, out, B, s));
         return TFHE_OK;
     }
@@ -743,7 +751,95 @@ tfhe_status dev_func(tfhe_ctx* c, Device& d, int prop, const uint64_t* ct, uint6
     HCHECK(launch_lwe_op(LWE_ADD_CONST, n, q, beta, ct2, nullptr, ct2, B, s));
     HCHECK(launch_lwe_op(LWE_SUB_CONST, n, q, q >> 2, ct2, nullptr, ct2, B, s));
     tv.mode = TV_LUT1;
-    return dev_bootstrap(c, d, tv, 0, ct2, out, B);
+    return dev_bootstrap(c, d, tv, 0, ct2, out, B, sel);
+}
+
+// ---------------------------------------------------------------------------
+// EvalFunc with one table per channel: ciphertext i of a flat batch uses table (i / inner) mod T
+// ---------------------------------------------------------------------------
+// The tables of one call, classified one by one on the host.  meta[t] = {class, class-0 / 1 / 2 tables below t}.
+struct TabCall {
+    const uint64_t* d_luts = nullptr;  // device [T][q]
+    size_t T = 0;
+    std::vector<uint8_t> cls;    // [T]
+    std::vector<uint32_t> meta;  // [T][4]
+    uint64_t ntab[3] = {};
+    int classes = 0;             // how many of the three are present
+    const uint4* d_meta = nullptr;  // Device::tab_meta, uploaded by tab_upload when classes > 1
+};
+
+void tab_classify(TabCall& tc, const uint64_t* luts, size_t T, uint64_t q) {
+    tc.T = T;
+    tc.cls.resize(T);
+    tc.meta.resize(4 * T);
+    for (size_t t = 0; t < T; ++t) {
+        const int k = check_input_function(luts + t * q, q, q);
+        tc.cls[t] = (uint8_t)k;
+        tc.meta[4 * t] = (uint32_t)k;
+        for (int j = 0; j < 3; ++j) tc.meta[4 * t + 1 + j] = (uint32_t)tc.ntab[j];
+        ++tc.ntab[k];
+    }
+    tc.classes = (tc.ntab[0] != 0) + (tc.ntab[1] != 0) + (tc.ntab[2] != 0);
+}
+
+// ciphertexts of each class below index i of the whole batch (k_tab_move computes the same number)
+void tab_count(const TabCall& tc, uint64_t inner, uint64_t i, uint64_t n[3]) {
+    const uint64_t period = inner * tc.T, p = i / period, r = i - p * period, t = r / inner, within = r - t * inner;
+    for (int k = 0; k < 3; ++k) n[k] = p * inner * tc.ntab[k] + inner * tc.meta[4 * t + 1 + k];
+    n[tc.cls[t]] += within;
+}
+
+// the class table on the device, inside the frame (the buffer is the scratch's: earlier users are done once the
+// stream reaches the copy); the host waits, so tc may go out of scope and a later call may overwrite tc.meta
+tfhe_status tab_upload(Device& d, TabCall& tc) {
+    if (tc.classes < 2) return TFHE_OK;
+    HCHECK(hipMemcpyAsync(d.tab_meta, tc.meta.data(), tc.T * 16, hipMemcpyHostToDevice, d.stream));
+    HCHECK(hipStreamSynchronize(d.stream));
+    tc.d_meta = reinterpret_cast<const uint4*>(d.tab_meta);
+    return TFHE_OK;
+}
+
+// One slice (B <= scratch capacity) whose row 0 is ciphertext `first` of the whole batch.  A slice of one class
+// runs dev_func on the caller's rows with the table chosen by the index rule: no row is copied.  Otherwise the
+// rows are gathered by class into lwe[3] (their tables into lwe[5]), each class present runs dev_func on its run
+// of rows into lwe[4], and the results are scattered: 2 + at most 3 pipelines, whatever T and inner are.
+tfhe_status dev_func_tables(tfhe_ctx* c, Device& d, const TabCall& tc, uint64_t inner, uint64_t first,
+                            const uint64_t* ct, uint64_t q, uint64_t* out, size_t B) {
+    uint64_t lo[3], hi[3];
+    tab_count(tc, inner, first, lo);
+    tab_count(tc, inner, first + B, hi);
+    int present = 0, only = 0;
+    for (int k = 0; k < 3; ++k)
+        if (hi[k] != lo[k]) ++present, only = k;
+    if (present == 1) {
+        const TabSel sel{nullptr, first, inner, tc.T};
+        return dev_func(c, d, only, ct, q, tc.d_luts, 0, out, B, &sel);
+    }
+    const size_t w = c->p.n + 1;
+    uint64_t *rows = d.sc.lwe[3], *res = d.sc.lwe[4];
+    uint32_t* ids = reinterpret_cast<uint32_t*>(d.sc.lwe[5]);
+    TabMove mv{};
+    mv.meta = tc.d_meta, mv.first = first, mv.count = B, mv.inner = inner, mv.T = tc.T, mv.width = (uint32_t)w;
+    uint64_t base = 0;
+    for (int k = 0; k < 3; ++k) mv.ntab[k] = tc.ntab[k], mv.lo[k] = lo[k], mv.base[k] = base, base += hi[k] - lo[k];
+    HCHECK(launch_tab_gather(mv, ct, rows, ids, d.stream));
+    for (int k = 0; k < 3; ++k) {
+        const size_t cnt = hi[k] - lo[k], at = mv.base[k];
+        if (cnt == 0) continue;
+        const TabSel sel{ids + at, 0, inner, tc.T};
+        SCHECK(dev_func(c, d, k, rows + at * w, q, tc.d_luts, 0, res + at * w, cnt, &sel));
+    }
+    HCHECK(launch_tab_scatter(mv, res, out, d.stream));
+    return TFHE_OK;
+}
+
+// a whole flat batch in slices of the scratch; the table index is the index in the batch, not in the slice
+tfhe_status dev_func_tables_batch(tfhe_ctx* c, Device& d, const TabCall& tc, uint64_t inner, const uint64_t* ct,
+                                  uint64_t q, uint64_t* out, size_t total) {
+    const size_t w = c->p.n + 1, slice = std::min(d.sc.cap, c->max_chunk);
+    for (size_t first = 0; first < total; first += slice)
+        SCHECK(dev_func_tables(c, d, tc, inner, first, ct + first * w, q, out + first * w, std::min(slice, total - first)));
+    return TFHE_OK;
 }
 
 // vector EvalFloor, binfhe-base-scheme.cpp:926-987.  out may alias nothing; uses lwe[3], lwe[4].
@@ -820,10 +916,12 @@ tfhe_status dev_mul_matrix(tfhe_ctx* c, Device& d, size_t instances, size_t K, c
 }
 
 // z = W^T x + bias mod q into d.dense_z, then EvalFunc over the flat batch of instances cols ciphertexts in
-// slices of the scratch, as dev_circuit slices a level
+// slices of the scratch, as dev_circuit slices a level.  tc: one table per column (inner = 1) instead of d_lut
 tfhe_status dev_dense(tfhe_ctx* c, Device& d, int prop, size_t instances, size_t K, const uint64_t* ct, size_t cols,
-                      const int64_t* matrix, const uint64_t* bias, uint64_t q, const uint64_t* d_lut, uint64_t* out) {
+                      const int64_t* matrix, const uint64_t* bias, uint64_t q, const uint64_t* d_lut, uint64_t* out,
+                      const TabCall* tc = nullptr) {
     SCHECK(dev_mul_matrix(c, d, instances, K, ct, cols, matrix, bias, q, d.dense_z));
+    if (tc) return dev_func_tables_batch(c, d, *tc, 1, d.dense_z, q, out, instances * cols);
     const size_t w = c->p.n + 1, total = instances * cols, slice = std::min(d.sc.cap, c->max_chunk);
     for (size_t first = 0; first < total; first += slice) {
         const size_t B = std::min(slice, total - first);
@@ -844,11 +942,14 @@ tfhe_status dev_conv2d(tfhe_ctx* c, Device& d, const ConvGeom& g, size_t instanc
 }
 
 // z = conv(x) + bias mod q into d.dense_z, then EvalFunc over the flat batch of instances c_out oh ow ciphertexts
-// in slices, as dev_dense
+// in slices, as dev_dense.  tc: one table per output plane (inner = oh ow) instead of d_lut
 tfhe_status dev_conv_layer(tfhe_ctx* c, Device& d, int prop, const ConvGeom& g, size_t instances, const uint64_t* ct,
                            const int64_t* weight, const uint64_t* bias, uint64_t q, const uint64_t* d_lut,
-                           uint64_t* out) {
+                           uint64_t* out, const TabCall* tc = nullptr) {
     SCHECK(dev_conv2d(c, d, g, instances, ct, weight, bias, q, d.dense_z));
+    if (tc)
+        return dev_func_tables_batch(c, d, *tc, (uint64_t)g.oh * g.ow, d.dense_z, q, out,
+                                     instances * g.c_out * g.oh * g.ow);
     const size_t w = c->p.n + 1, total = instances * g.c_out * g.oh * g.ow, slice = std::min(d.sc.cap, c->max_chunk);
     for (size_t first = 0; first < total; first += slice) {
         const size_t B = std::min(slice, total - first);
@@ -863,9 +964,11 @@ tfhe_status dev_conv_layer(tfhe_ctx* c, Device& d, int prop, const ConvGeom& g, 
 // Round by round: the round's pairs over every instance and plane are one flat batch, item = plane nrec + record;
 // per slice of the scratch, z = a - b into the first half of d.dense_z, EvalFunc into the second, dst = f + b into
 // d.pool_slots or out.  A round reads inputs and earlier rounds' slots and writes fresh slots and outputs, so
-// its slices are independent.  Positions with one valid tap are copied.
+// its slices are independent.  Positions with one valid tap are copied.  tc: one table per plane instead of d_lut
+// (item = plane nrec + record, so inner is the round's nrec and the table is plane mod c).
 tfhe_status dev_pool2d(tfhe_ctx* c, Device& d, int prop, const Device::PoolPlanDev& pp, size_t instances,
-                       const uint64_t* ct, uint64_t q, const uint64_t* d_lut, uint64_t* out) {
+                       const uint64_t* ct, uint64_t q, const uint64_t* d_lut, uint64_t* out,
+                       const TabCall* tc = nullptr) {
     const PoolGeom& g = pp.g;
     const size_t w = c->p.n + 1, planes = instances * g.c, slice = std::min(d.sc.cap, c->max_chunk);
     PoolArgs a{};
@@ -881,7 +984,8 @@ tfhe_status dev_pool2d(tfhe_ctx* c, Device& d, int prop, const Device::PoolPlanD
         for (a.first = 0; a.first < total; a.first += slice) {
             a.count = std::min(slice, total - a.first);
             HCHECK(launch_pool_diff(a, z, d.stream));
-            SCHECK(dev_func(c, d, prop, z, q, d_lut, 0, f, a.count));
+            if (tc) SCHECK(dev_func_tables(c, d, *tc, a.nrec, a.first, z, q, f, a.count));
+            else SCHECK(dev_func(c, d, prop, z, q, d_lut, 0, f, a.count));
             HCHECK(launch_pool_add(a, f, d.stream));
         }
     }
@@ -2431,6 +2535,137 @@ tfhe_status run_device_op(tfhe_ctx* c, size_t B, const void* d_out, void* stream
 }  // namespace
 }  // extern "C++"
 
+extern "C++" {
+namespace {
+// What every call with one table per channel checks of (q, num_luts, inner) before any device call (N = 0: no
+// context, q need only be a power of two >= 8); every message names the field.
+tfhe_status check_tables_args(const char* who, uint64_t q, uint64_t N, size_t num_luts, size_t inner) {
+    const auto bad = [who](const std::string& what) {
+        return fail(TFHE_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what);
+    };
+    if (num_luts == 0) return bad("num_luts is 0");
+    if (inner == 0) return bad("inner is 0");
+    if (q < 8 || (q & (q - 1)) != 0 || (N && (2ull * N) % q != 0))
+        return bad(N ? "q must be a power of two >= 8 that divides 2N" : "q must be a power of two >= 8");
+    if (num_luts > UINT32_MAX || num_luts > SIZE_MAX / sizeof(uint64_t) / q) return bad("num_luts q overflows");
+    if (inner > SIZE_MAX / num_luts) return bad("inner num_luts overflows");
+    return TFHE_OK;
+}
+
+// The host tables of a host-array call: an arbitrary one at q > N is refused before anything is allocated or
+// launched.  num_luts = 0: one shared table; else lut[num_luts][q], classified once into `pre` for tab_prepare.
+tfhe_status check_host_tables(tfhe_ctx* c, const uint64_t* lut, size_t num_luts, uint64_t q, TabCall& pre) {
+    bool arbitrary;
+    if (num_luts) {
+        tab_classify(pre, lut, num_luts, q);
+        arbitrary = pre.ntab[2] != 0;
+    } else {
+        arbitrary = check_input_function(lut, q, q) == 2;
+    }
+    if (arbitrary && q > c->p.N) return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
+    return TFHE_OK;
+}
+
+// The tables of a device call, before its frame opens: the T q words read back once and classified one by one,
+// the call refused when an arbitrary table meets q > N, and the class table's store in place.  pre: the classes
+// of the same tables, known already (the host-array forms classify their host copy: no read-back, no second pass).
+tfhe_status tab_prepare(tfhe_ctx* c, Device& d, void* stream, uint64_t q, const uint64_t* d_luts, size_t T, TabCall& tc,
+                        const TabCall* pre = nullptr) {
+    if (pre) {
+        tc = *pre;
+    } else {
+        std::vector<uint64_t> host(T * q);
+        hipStream_t s = stream ? (hipStream_t)stream : d.stream;
+        HCHECK(hipMemcpyAsync(host.data(), d_luts, T * q * 8, hipMemcpyDeviceToHost, s));
+        HCHECK(hipStreamSynchronize(s));
+        tab_classify(tc, host.data(), T, q);
+    }
+    tc.d_luts = d_luts;
+    if (tc.ntab[2] && q > c->p.N) return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
+    if (tc.classes > 1) SCHECK(ensure_words(d, d.tab_meta, d.tab_meta_words, 2 * T));
+    return TFHE_OK;
+}
+
+tfhe_status check_func_tables_call(tfhe_ctx* c, size_t B, const void* ct, uint64_t q, const void* luts, size_t num_luts,
+                                   size_t inner, const void* out) {
+    SCHECK(check_ctx(c));
+    if (!ct) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalFuncTables: null ct");
+    if (!luts) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalFuncTables: null luts");
+    if (!out) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalFuncTables: null out");
+    if (B == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalFuncTables: B is 0");
+    SCHECK(check_tables_args("EvalFuncTables", q, c->p.N, num_luts, inner));
+    if (B > SIZE_MAX / sizeof(uint64_t) / (c->p.n + 1)) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalFuncTables: B (n+1) overflows");
+    return TFHE_OK;
+}
+
+// d_out selects the device
+tfhe_status func_tables_on_device(tfhe_ctx* c, size_t B, const uint64_t* d_ct, uint64_t q, const uint64_t* d_luts,
+                                  size_t num_luts, size_t inner, uint64_t* d_out, void* stream,
+                                  const TabCall* pre = nullptr) {
+    Device* dp = nullptr;
+    SCHECK(device_for(c, d_out, dp));
+    HCHECK(hipSetDevice(dp->id));
+    TabCall tc;
+    SCHECK(tab_prepare(c, *dp, stream, q, d_luts, num_luts, tc, pre));
+    return run_device_op(c, std::min(B, c->max_chunk), d_out, stream, [&](Device& d) {
+        SCHECK(tab_upload(d, tc));
+        return dev_func_tables_batch(c, d, tc, inner, d_ct, q, d_out, B);
+    });
+}
+}  // namespace
+}  // extern "C++"
+
+tfhe_status tfhe_lut_tables_info(uint64_t q, const uint64_t* luts, size_t num_luts, size_t inner, size_t B,
+                                 uint8_t* classes, size_t per_class[3], uint64_t* bootstraps) {
+    return guarded([&]() -> tfhe_status {
+        if (!luts) return fail(TFHE_ERR_INVALID_ARGUMENT, "LutTablesInfo: null luts");
+        if (!per_class) return fail(TFHE_ERR_INVALID_ARGUMENT, "LutTablesInfo: null per_class");
+        if (!bootstraps) return fail(TFHE_ERR_INVALID_ARGUMENT, "LutTablesInfo: null bootstraps");
+        if (B == 0) return fail(TFHE_ERR_INVALID_ARGUMENT, "LutTablesInfo: B is 0");
+        SCHECK(check_tables_args("LutTablesInfo", q, 0, num_luts, inner));
+        TabCall tc;
+        tab_classify(tc, luts, num_luts, q);
+        if (classes) std::copy(tc.cls.begin(), tc.cls.end(), classes);
+        uint64_t n[3];
+        tab_count(tc, inner, B, n);
+        for (int k = 0; k < 3; ++k) per_class[k] = (size_t)n[k];
+        *bootstraps = n[0] + 2 * (n[1] + n[2]);
+        return TFHE_OK;
+    });
+}
+
+tfhe_status tfhe_eval_func_tables_device(tfhe_ctx* c, size_t B, const uint64_t* d_ct, uint64_t q, const uint64_t* d_luts,
+                                         size_t num_luts, size_t inner, uint64_t* d_out, void* stream) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_func_tables_call(c, B, d_ct, q, d_luts, num_luts, inner, d_out));
+        return func_tables_on_device(c, B, d_ct, q, d_luts, num_luts, inner, d_out, stream);
+    });
+}
+
+tfhe_status tfhe_eval_func_tables(tfhe_ctx* c, size_t B, const uint64_t* ct, uint64_t q, const uint64_t* luts,
+                                  size_t num_luts, size_t inner, uint64_t* out) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_func_tables_call(c, B, ct, q, luts, num_luts, inner, out));
+        TabCall pre;
+        SCHECK(check_host_tables(c, luts, num_luts, q, pre));
+        Device& d = c->devs[0];
+        HCHECK(hipSetDevice(d.id));
+        const size_t w = c->p.n + 1, wc = B * w, wl = num_luts * q;
+        if (wc > (SIZE_MAX / sizeof(uint64_t) - wl) / 2) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalFuncTables: sizes overflow");
+        // one block: ct | luts | out
+        DevBuf buf;
+        HCHECK(hipMalloc(&buf.p, (wc + wl + wc) * sizeof(uint64_t)));
+        uint64_t *dct = buf.as<uint64_t>(), *dl = dct + wc, *dout = dl + wl;
+        tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wc, d.stream);
+        if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(luts, q), wl, d.stream);
+        if (st == TFHE_OK) st = func_tables_on_device(c, B, dct, q, dl, num_luts, inner, dout, nullptr, &pre);
+        if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wc, d.stream);
+        const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
+        if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalFuncTables: ") + hipGetErrorString(e));
+        return st;
+    });
+}
+
 tfhe_status tfhe_eval_bin_gate_device(tfhe_ctx* c, int gate, size_t B, const uint64_t* d_ct1, const uint64_t* d_ct2,
                                       uint64_t q, uint64_t* d_out, void* stream) {
     return guarded([&]() -> tfhe_status {
@@ -2768,13 +3003,24 @@ tfhe_status check_dense_call(tfhe_ctx* c, size_t instances, size_t K, const void
     return TFHE_OK;
 }
 
-// d_out selects the device; the table's class comes from its first q words, read back once
+// d_out selects the device; the table's class comes from its first q words, read back once.  num_luts > 0:
+// d_lut is [num_luts = cols][q], one table per column
 tfhe_status dense_on_device(tfhe_ctx* c, size_t instances, size_t K, const uint64_t* d_ct, size_t cols,
                             const int64_t* d_matrix, const uint64_t* d_bias, uint64_t q, const uint64_t* d_lut,
-                            uint64_t* d_out, void* stream) {
+                            uint64_t* d_out, void* stream, size_t num_luts = 0, const TabCall* pre = nullptr) {
     Device* dp = nullptr;
     SCHECK(device_for(c, d_out, dp));
     HCHECK(hipSetDevice(dp->id));
+    if (num_luts) {
+        TabCall tc;
+        SCHECK(tab_prepare(c, *dp, stream, q, d_lut, num_luts, tc, pre));
+        SCHECK(ensure_words(*dp, dp->mm_mat, dp->mm_mat_words, K * cols));
+        SCHECK(ensure_words(*dp, dp->dense_z, dp->dense_z_words, instances * cols * (c->p.n + 1)));
+        return run_device_op(c, std::min(instances * cols, c->max_chunk), d_out, stream, [&](Device& d) {
+            SCHECK(tab_upload(d, tc));
+            return dev_dense(c, d, 0, instances, K, d_ct, cols, d_matrix, d_bias, q, d_lut, d_out, &tc);
+        });
+    }
     std::vector<uint64_t> lut0(q);
     hipStream_t s = stream ? (hipStream_t)stream : dp->stream;
     HCHECK(hipMemcpyAsync(lut0.data(), d_lut, q * 8, hipMemcpyDeviceToHost, s));
@@ -2846,32 +3092,72 @@ tfhe_status tfhe_eval_dense_device(tfhe_ctx* c, size_t instances, size_t K, cons
     });
 }
 
+extern "C++" {
+namespace {
+// what the layers with one table per channel check on top of the layer's own rules
+tfhe_status check_layer_tables(tfhe_ctx* c, const char* who, uint64_t q, size_t num_luts, size_t channels,
+                               const char* channels_name) {
+    SCHECK(check_tables_args(who, q, c->p.N, num_luts, 1));
+    if (num_luts != channels)
+        return fail(TFHE_ERR_INVALID_ARGUMENT, std::string(who) + ": num_luts must equal " + channels_name);
+    return TFHE_OK;
+}
+
+// the host-array dense layer; num_luts = 0: one shared table, else lut[num_luts = cols][q]
+tfhe_status dense_from_host(tfhe_ctx* c, size_t instances, size_t K, const uint64_t* ct, size_t cols,
+                            const int64_t* matrix, const uint64_t* bias, uint64_t q, const uint64_t* lut,
+                            uint64_t* out, size_t num_luts) {
+    TabCall pre;
+    SCHECK(check_host_tables(c, lut, num_luts, q, pre));
+    Device& d = c->devs[0];
+    HCHECK(hipSetDevice(d.id));
+    const size_t w = c->p.n + 1, wi = instances * K * w, wm = K * cols, wo = instances * cols * w,
+                 wl = std::max<size_t>(num_luts, 1) * q;
+    // one block: ct | matrix | bias | lut | out
+    DevBuf buf;
+    HCHECK(hipMalloc(&buf.p, (wi + wm + cols + wl + wo) * sizeof(uint64_t)));
+    uint64_t *dct = buf.as<uint64_t>(), *dm = dct + wi, *db = dm + wm, *dl = db + cols, *dout = dl + wl;
+    tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wi, d.stream);
+    if (st == TFHE_OK) st = h2d_staged(d, dm, flat_rows(reinterpret_cast<const uint64_t*>(matrix), cols), wm, d.stream);
+    if (st == TFHE_OK && bias) st = h2d_staged(d, db, flat_rows(bias, cols), cols, d.stream);
+    if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(lut, q), wl, d.stream);
+    if (st == TFHE_OK)
+        st = dense_on_device(c, instances, K, dct, cols, reinterpret_cast<const int64_t*>(dm), bias ? db : nullptr, q,
+                             dl, dout, nullptr, num_luts, num_luts ? &pre : nullptr);
+    if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
+    const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
+    if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalDense: ") + hipGetErrorString(e));
+    return st;
+}
+}  // namespace
+}  // extern "C++"
+
 tfhe_status tfhe_eval_dense(tfhe_ctx* c, size_t instances, size_t K, const uint64_t* ct, size_t cols,
                             const int64_t* matrix, const uint64_t* bias, uint64_t q, const uint64_t* lut,
                             uint64_t* out) {
     return guarded([&]() -> tfhe_status {
         SCHECK(check_dense_call(c, instances, K, ct, cols, matrix, q, lut, out));
-        // the class is known from the host table: refuse before anything is allocated or launched
-        if (check_input_function(lut, q, q) == 2 && q > c->p.N)
-            return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
-        Device& d = c->devs[0];
-        HCHECK(hipSetDevice(d.id));
-        const size_t w = c->p.n + 1, wi = instances * K * w, wm = K * cols, wo = instances * cols * w;
-        // one block: ct | matrix | bias | lut | out
-        DevBuf buf;
-        HCHECK(hipMalloc(&buf.p, (wi + wm + cols + q + wo) * sizeof(uint64_t)));
-        uint64_t *dct = buf.as<uint64_t>(), *dm = dct + wi, *db = dm + wm, *dl = db + cols, *dout = dl + q;
-        tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wi, d.stream);
-        if (st == TFHE_OK) st = h2d_staged(d, dm, flat_rows(reinterpret_cast<const uint64_t*>(matrix), cols), wm, d.stream);
-        if (st == TFHE_OK && bias) st = h2d_staged(d, db, flat_rows(bias, cols), cols, d.stream);
-        if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(lut, q), q, d.stream);
-        if (st == TFHE_OK)
-            st = dense_on_device(c, instances, K, dct, cols, reinterpret_cast<const int64_t*>(dm), bias ? db : nullptr, q,
-                                 dl, dout, nullptr);
-        if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
-        const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
-        if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalDense: ") + hipGetErrorString(e));
-        return st;
+        return dense_from_host(c, instances, K, ct, cols, matrix, bias, q, lut, out, 0);
+    });
+}
+
+tfhe_status tfhe_eval_dense_tables_device(tfhe_ctx* c, size_t instances, size_t K, const uint64_t* d_ct, size_t cols,
+                                          const int64_t* d_matrix, const uint64_t* d_bias, uint64_t q,
+                                          const uint64_t* d_luts, size_t num_luts, uint64_t* d_out, void* stream) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_dense_call(c, instances, K, d_ct, cols, d_matrix, q, d_luts, d_out));
+        SCHECK(check_layer_tables(c, "EvalDense", q, num_luts, cols, "cols"));
+        return dense_on_device(c, instances, K, d_ct, cols, d_matrix, d_bias, q, d_luts, d_out, stream, num_luts);
+    });
+}
+
+tfhe_status tfhe_eval_dense_tables(tfhe_ctx* c, size_t instances, size_t K, const uint64_t* ct, size_t cols,
+                                   const int64_t* matrix, const uint64_t* bias, uint64_t q, const uint64_t* luts,
+                                   size_t num_luts, uint64_t* out) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_dense_call(c, instances, K, ct, cols, matrix, q, luts, out));
+        SCHECK(check_layer_tables(c, "EvalDense", q, num_luts, cols, "cols"));
+        return dense_from_host(c, instances, K, ct, cols, matrix, bias, q, luts, out, num_luts);
     });
 }
 
@@ -2954,13 +3240,25 @@ tfhe_status check_conv_layer_call(tfhe_ctx* c, const tfhe_conv2d* desc, size_t i
     return TFHE_OK;
 }
 
-// d_out selects the device; the table's class comes from its first q words, read back once
+// d_out selects the device; the table's class comes from its first q words, read back once.  num_luts > 0:
+// d_lut is [num_luts = c_out][q], one table per output plane
 tfhe_status conv_layer_on_device(tfhe_ctx* c, const ConvGeom& g, size_t K, size_t instances, const uint64_t* d_ct,
                                  const int64_t* d_weight, const uint64_t* d_bias, uint64_t q, const uint64_t* d_lut,
-                                 uint64_t* d_out, void* stream) {
+                                 uint64_t* d_out, void* stream, size_t num_luts = 0, const TabCall* pre = nullptr) {
     Device* dp = nullptr;
     SCHECK(device_for(c, d_out, dp));
     HCHECK(hipSetDevice(dp->id));
+    if (num_luts) {
+        TabCall tc;
+        SCHECK(tab_prepare(c, *dp, stream, q, d_lut, num_luts, tc, pre));
+        const size_t total = instances * g.c_out * g.oh * g.ow;
+        SCHECK(ensure_words(*dp, dp->mm_mat, dp->mm_mat_words, K * g.c_out));
+        SCHECK(ensure_words(*dp, dp->dense_z, dp->dense_z_words, total * (c->p.n + 1)));
+        return run_device_op(c, std::min(total, c->max_chunk), d_out, stream, [&](Device& d) {
+            SCHECK(tab_upload(d, tc));
+            return dev_conv_layer(c, d, 0, g, instances, d_ct, d_weight, d_bias, q, d_lut, d_out, &tc);
+        });
+    }
     std::vector<uint64_t> lut0(q);
     hipStream_t s = stream ? (hipStream_t)stream : dp->stream;
     HCHECK(hipMemcpyAsync(lut0.data(), d_lut, q * 8, hipMemcpyDeviceToHost, s));
@@ -3017,6 +3315,37 @@ tfhe_status tfhe_eval_conv2d_device(tfhe_ctx* c, const tfhe_conv2d* desc, size_t
     });
 }
 
+extern "C++" {
+namespace {
+// the host-array convolution layer; num_luts = 0: one shared table, else lut[num_luts = c_out][q]
+tfhe_status conv_layer_from_host(tfhe_ctx* c, const ConvGeom& g, size_t K, size_t instances, const uint64_t* ct,
+                                 const int64_t* weight, const uint64_t* bias, uint64_t q, const uint64_t* lut,
+                                 uint64_t* out, size_t num_luts) {
+    TabCall pre;
+    SCHECK(check_host_tables(c, lut, num_luts, q, pre));
+    Device& d = c->devs[0];
+    HCHECK(hipSetDevice(d.id));
+    const size_t w = c->p.n + 1, wi = instances * g.c_in * g.h * g.w * w, wm = K * g.c_out, nb = g.c_out,
+                 wo = instances * g.c_out * g.oh * g.ow * w, wl = std::max<size_t>(num_luts, 1) * q;
+    // one block: ct | weight | bias | lut | out
+    DevBuf buf;
+    HCHECK(hipMalloc(&buf.p, (wi + wm + nb + wl + wo) * sizeof(uint64_t)));
+    uint64_t *dct = buf.as<uint64_t>(), *dm = dct + wi, *db = dm + wm, *dl = db + nb, *dout = dl + wl;
+    tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wi, d.stream);
+    if (st == TFHE_OK) st = h2d_staged(d, dm, flat_rows(reinterpret_cast<const uint64_t*>(weight), K), wm, d.stream);
+    if (st == TFHE_OK && bias) st = h2d_staged(d, db, flat_rows(bias, nb), nb, d.stream);
+    if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(lut, q), wl, d.stream);
+    if (st == TFHE_OK)
+        st = conv_layer_on_device(c, g, K, instances, dct, reinterpret_cast<const int64_t*>(dm), bias ? db : nullptr,
+                                  q, dl, dout, nullptr, num_luts, num_luts ? &pre : nullptr);
+    if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
+    const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
+    if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalConv2d: ") + hipGetErrorString(e));
+    return st;
+}
+}  // namespace
+}  // extern "C++"
+
 tfhe_status tfhe_eval_conv2d(tfhe_ctx* c, const tfhe_conv2d* desc, size_t instances, const uint64_t* ct,
                              const int64_t* weight, const uint64_t* bias, uint64_t q, const uint64_t* lut,
                              uint64_t* out) {
@@ -3024,28 +3353,31 @@ tfhe_status tfhe_eval_conv2d(tfhe_ctx* c, const tfhe_conv2d* desc, size_t instan
         ConvGeom g;
         size_t K = 0;
         SCHECK(check_conv_layer_call(c, desc, instances, ct, weight, q, lut, out, g, K));
-        // the class is known from the host table: refuse before anything is allocated or launched
-        if (check_input_function(lut, q, q) == 2 && q > c->p.N)
-            return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
-        Device& d = c->devs[0];
-        HCHECK(hipSetDevice(d.id));
-        const size_t w = c->p.n + 1, wi = instances * g.c_in * g.h * g.w * w, wm = K * g.c_out, nb = g.c_out,
-                     wo = instances * g.c_out * g.oh * g.ow * w;
-        // one block: ct | weight | bias | lut | out
-        DevBuf buf;
-        HCHECK(hipMalloc(&buf.p, (wi + wm + nb + q + wo) * sizeof(uint64_t)));
-        uint64_t *dct = buf.as<uint64_t>(), *dm = dct + wi, *db = dm + wm, *dl = db + nb, *dout = dl + q;
-        tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wi, d.stream);
-        if (st == TFHE_OK) st = h2d_staged(d, dm, flat_rows(reinterpret_cast<const uint64_t*>(weight), K), wm, d.stream);
-        if (st == TFHE_OK && bias) st = h2d_staged(d, db, flat_rows(bias, nb), nb, d.stream);
-        if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(lut, q), q, d.stream);
-        if (st == TFHE_OK)
-            st = conv_layer_on_device(c, g, K, instances, dct, reinterpret_cast<const int64_t*>(dm), bias ? db : nullptr,
-                                      q, dl, dout, nullptr);
-        if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
-        const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
-        if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalConv2d: ") + hipGetErrorString(e));
-        return st;
+        return conv_layer_from_host(c, g, K, instances, ct, weight, bias, q, lut, out, 0);
+    });
+}
+
+tfhe_status tfhe_eval_conv2d_tables_device(tfhe_ctx* c, const tfhe_conv2d* desc, size_t instances, const uint64_t* d_ct,
+                                           const int64_t* d_weight, const uint64_t* d_bias, uint64_t q,
+                                           const uint64_t* d_luts, size_t num_luts, uint64_t* d_out, void* stream) {
+    return guarded([&]() -> tfhe_status {
+        ConvGeom g;
+        size_t K = 0;
+        SCHECK(check_conv_layer_call(c, desc, instances, d_ct, d_weight, q, d_luts, d_out, g, K));
+        SCHECK(check_layer_tables(c, "EvalConv2d", q, num_luts, g.c_out, "c_out"));
+        return conv_layer_on_device(c, g, K, instances, d_ct, d_weight, d_bias, q, d_luts, d_out, stream, num_luts);
+    });
+}
+
+tfhe_status tfhe_eval_conv2d_tables(tfhe_ctx* c, const tfhe_conv2d* desc, size_t instances, const uint64_t* ct,
+                                    const int64_t* weight, const uint64_t* bias, uint64_t q, const uint64_t* luts,
+                                    size_t num_luts, uint64_t* out) {
+    return guarded([&]() -> tfhe_status {
+        ConvGeom g;
+        size_t K = 0;
+        SCHECK(check_conv_layer_call(c, desc, instances, ct, weight, q, luts, out, g, K));
+        SCHECK(check_layer_tables(c, "EvalConv2d", q, num_luts, g.c_out, "c_out"));
+        return conv_layer_from_host(c, g, K, instances, ct, weight, bias, q, luts, out, num_luts);
     });
 }
 
@@ -3124,12 +3456,27 @@ tfhe_status pool_plan_on_device(Device& d, const PoolGeom& g, const Device::Pool
     return TFHE_OK;
 }
 
-// d_out selects the device; the table's class comes from its first q words, read back once
+// d_out selects the device; the table's class comes from its first q words, read back once.  num_luts > 0:
+// d_lut is [num_luts = c][q], one table per plane
 tfhe_status pool_on_device(tfhe_ctx* c, const PoolGeom& g, size_t instances, const uint64_t* d_ct, uint64_t q,
-                           const uint64_t* d_lut, uint64_t* d_out, void* stream) {
+                           const uint64_t* d_lut, uint64_t* d_out, void* stream, size_t num_luts = 0,
+                           const TabCall* pre = nullptr) {
     Device* dp = nullptr;
     SCHECK(device_for(c, d_out, dp));
     HCHECK(hipSetDevice(dp->id));
+    if (num_luts) {
+        TabCall tc;
+        SCHECK(tab_prepare(c, *dp, stream, q, d_lut, num_luts, tc, pre));
+        const Device::PoolPlanDev* pp = nullptr;
+        SCHECK(pool_plan_on_device(*dp, g, pp));
+        const size_t w = c->p.n + 1, planes = instances * g.c, B = std::min(planes * pp->widest, c->max_chunk);
+        SCHECK(ensure_words(*dp, dp->dense_z, dp->dense_z_words, 2 * B * w));
+        SCHECK(ensure_words(*dp, dp->pool_slots, dp->pool_slots_words, planes * pp->slots * w));
+        return run_device_op(c, B, d_out, stream, [&](Device& d) {
+            SCHECK(tab_upload(d, tc));
+            return dev_pool2d(c, d, 0, *pp, instances, d_ct, q, d_lut, d_out, &tc);
+        });
+    }
     std::vector<uint64_t> lut0(q);
     hipStream_t s = stream ? (hipStream_t)stream : dp->stream;
     HCHECK(hipMemcpyAsync(lut0.data(), d_lut, q * 8, hipMemcpyDeviceToHost, s));
@@ -3184,6 +3531,32 @@ tfhe_status tfhe_eval_pool2d_device(tfhe_ctx* c, const tfhe_pool2d* desc, size_t
     });
 }
 
+extern "C++" {
+namespace {
+// the host-array pooling layer; num_luts = 0: one shared table, else lut[num_luts = c][q]
+tfhe_status pool_from_host(tfhe_ctx* c, const PoolGeom& g, size_t instances, const uint64_t* ct, uint64_t q,
+                           const uint64_t* lut, uint64_t* out, size_t num_luts) {
+    TabCall pre;
+    SCHECK(check_host_tables(c, lut, num_luts, q, pre));
+    Device& d = c->devs[0];
+    HCHECK(hipSetDevice(d.id));
+    const size_t w = c->p.n + 1, wi = instances * g.c * g.h * g.w * w, wo = instances * g.c * g.oh * g.ow * w,
+                 wl = std::max<size_t>(num_luts, 1) * q;
+    // one block: ct | lut | out
+    DevBuf buf;
+    HCHECK(hipMalloc(&buf.p, (wi + wl + wo) * sizeof(uint64_t)));
+    uint64_t *dct = buf.as<uint64_t>(), *dl = dct + wi, *dout = dl + wl;
+    tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wi, d.stream);
+    if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(lut, q), wl, d.stream);
+    if (st == TFHE_OK) st = pool_on_device(c, g, instances, dct, q, dl, dout, nullptr, num_luts, num_luts ? &pre : nullptr);
+    if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
+    const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
+    if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalPool2d: ") + hipGetErrorString(e));
+    return st;
+}
+}  // namespace
+}  // extern "C++"
+
 tfhe_status tfhe_eval_pool2d(tfhe_ctx* c, const tfhe_pool2d* desc, size_t instances, const uint64_t* ct, uint64_t q,
                              const uint64_t* lut, uint64_t* out) {
     return guarded([&]() -> tfhe_status {
@@ -3191,23 +3564,32 @@ tfhe_status tfhe_eval_pool2d(tfhe_ctx* c, const tfhe_pool2d* desc, size_t instan
         PoolGeom g;
         size_t pairs = 0;
         SCHECK(check_pool_args("EvalPool2d", desc, instances, ct, q, c->p.N, lut, out, c->p.n + 1, g, pairs));
-        // the class is known from the host table: refuse before anything is allocated or launched
-        if (check_input_function(lut, q, q) == 2 && q > c->p.N)
-            return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
-        Device& d = c->devs[0];
-        HCHECK(hipSetDevice(d.id));
-        const size_t w = c->p.n + 1, wi = instances * g.c * g.h * g.w * w, wo = instances * g.c * g.oh * g.ow * w;
-        // one block: ct | lut | out
-        DevBuf buf;
-        HCHECK(hipMalloc(&buf.p, (wi + q + wo) * sizeof(uint64_t)));
-        uint64_t *dct = buf.as<uint64_t>(), *dl = dct + wi, *dout = dl + q;
-        tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wi, d.stream);
-        if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(lut, q), q, d.stream);
-        if (st == TFHE_OK) st = pool_on_device(c, g, instances, dct, q, dl, dout, nullptr);
-        if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
-        const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
-        if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalPool2d: ") + hipGetErrorString(e));
-        return st;
+        return pool_from_host(c, g, instances, ct, q, lut, out, 0);
+    });
+}
+
+tfhe_status tfhe_eval_pool2d_tables_device(tfhe_ctx* c, const tfhe_pool2d* desc, size_t instances, const uint64_t* d_ct,
+                                           uint64_t q, const uint64_t* d_luts, size_t num_luts, uint64_t* d_out,
+                                           void* stream) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_ctx(c));
+        PoolGeom g;
+        size_t pairs = 0;
+        SCHECK(check_pool_args("EvalPool2d", desc, instances, d_ct, q, c->p.N, d_luts, d_out, c->p.n + 1, g, pairs));
+        SCHECK(check_layer_tables(c, "EvalPool2d", q, num_luts, g.c, "c"));
+        return pool_on_device(c, g, instances, d_ct, q, d_luts, d_out, stream, num_luts);
+    });
+}
+
+tfhe_status tfhe_eval_pool2d_tables(tfhe_ctx* c, const tfhe_pool2d* desc, size_t instances, const uint64_t* ct,
+                                    uint64_t q, const uint64_t* luts, size_t num_luts, uint64_t* out) {
+    return guarded([&]() -> tfhe_status {
+        SCHECK(check_ctx(c));
+        PoolGeom g;
+        size_t pairs = 0;
+        SCHECK(check_pool_args("EvalPool2d", desc, instances, ct, q, c->p.N, luts, out, c->p.n + 1, g, pairs));
+        SCHECK(check_layer_tables(c, "EvalPool2d", q, num_luts, g.c, "c"));
+        return pool_from_host(c, g, instances, ct, q, luts, out, num_luts);
     });
 }
 

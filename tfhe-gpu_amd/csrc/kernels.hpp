@@ -182,6 +182,30 @@ struct TvParams {
 // ct[B][n+1] -> acc[B][2][N] (acc0 = 0, acc1 = test vector), a_out[B][n] = a part
 hipError_t launch_build_testvector(const TvParams& P, const uint64_t* ct, uint64_t* acc, uint64_t* a_out, size_t B,
                                    hipStream_t s);
+// ---- one table per channel (func_tables.hip) ----
+// Which table of P.lut[T][P.lut_len] row s of a launch reads: ids[s] when ids is set (a class's gathered rows), else
+// ((first + s) / inner) mod T, first the row's index in the whole batch.
+struct TabSel {
+    const uint32_t* ids;
+    uint64_t first, inner, T;
+};
+// launch_build_testvector for the modes TV_LUT, TV_LUT1 and TV_LUT2 with the table chosen by S; q a power of two
+hipError_t launch_build_testvector_tab(const TvParams& P, const TabSel& S, const uint64_t* ct, uint64_t* acc,
+                                       uint64_t* a_out, size_t B, hipStream_t s);
+// A slice [first, first + count) of the batch that holds several classes, moved to and from per-class runs of rows:
+// an item of class c goes to row base[c] + its rank among the slice's class-c items.  meta[T] = {class, number of
+// class-0 / 1 / 2 tables below t}; ntab[c] the class's tables; lo[c] the class's items below `first`.
+struct TabMove {
+    const uint4* meta;
+    uint64_t first, count, inner, T;
+    uint64_t ntab[3], lo[3], base[3];
+    uint32_t width;
+};
+// rows[pos] = flat[s] and ids[pos] = the item's table, for s < count
+hipError_t launch_tab_gather(const TabMove& M, const uint64_t* flat, uint64_t* rows, uint32_t* ids, hipStream_t s);
+// flat[s] = rows[pos]
+hipError_t launch_tab_scatter(const TabMove& M, const uint64_t* rows, uint64_t* flat, hipStream_t s);
+
 // tv[B][tvlen] -> acc[B][2][N]: acc0 = 0, acc1[j * (N / tvlen)] = tv[j], other coefficients 0
 hipError_t launch_expand_tv(uint32_t N, uint32_t tvlen, const uint64_t* tv, uint64_t* acc, size_t B, hipStream_t s);
 // u16 / u32 (wb = 2 / 4 bytes) <-> u64 words: the narrow PCIe wire format of the host-array runner

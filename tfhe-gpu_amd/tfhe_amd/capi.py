@@ -174,6 +174,15 @@ _SIGS = {
     "tfhe_pool2d_eval_plain": ([VP, SZ, U64, VP, VP, VP], C.c_int),
     "tfhe_eval_pool2d_device": ([VP, VP, SZ, VP, U64, VP, VP, VP], C.c_int),
     "tfhe_eval_pool2d": ([VP, VP, SZ, u64p, U64, u64p, u64p], C.c_int),
+    "tfhe_lut_tables_info": ([U64, VP, SZ, SZ, SZ, VP, C.POINTER(SZ), C.POINTER(U64)], C.c_int),
+    "tfhe_eval_func_tables_device": ([VP, SZ, VP, U64, VP, SZ, SZ, VP, VP], C.c_int),
+    "tfhe_eval_func_tables": ([VP, SZ, u64p, U64, u64p, SZ, SZ, u64p], C.c_int),
+    "tfhe_eval_dense_tables_device": ([VP, SZ, SZ, VP, SZ, VP, VP, U64, VP, SZ, VP, VP], C.c_int),
+    "tfhe_eval_dense_tables": ([VP, SZ, SZ, u64p, SZ, i64p, VP, U64, u64p, SZ, u64p], C.c_int),
+    "tfhe_eval_conv2d_tables_device": ([VP, VP, SZ, VP, VP, VP, U64, VP, SZ, VP, VP], C.c_int),
+    "tfhe_eval_conv2d_tables": ([VP, VP, SZ, u64p, i64p, VP, U64, u64p, SZ, u64p], C.c_int),
+    "tfhe_eval_pool2d_tables_device": ([VP, VP, SZ, VP, U64, VP, SZ, VP, VP], C.c_int),
+    "tfhe_eval_pool2d_tables": ([VP, VP, SZ, u64p, U64, u64p, SZ, u64p], C.c_int),
     "tfhe_keygen_device": ([P, U64, C.c_int, VP, VP, VP, C.POINTER(U64), VP], C.c_int),
     "tfhe_setup_keygen": ([C.POINTER(VP), P, U64, C.c_int, u64p, C.POINTER(U64)], C.c_int),
     "tfhe_encrypt_device": ([P, C.c_int, VP, SZ, VP, U64, U64, U64, VP, C.POINTER(U64), VP], C.c_int),
@@ -317,6 +326,27 @@ def pool2d_eval_plain(desc: Pool2d, values, lut, q: int):
                                        C.c_void_p(x.ctypes.data), C.c_void_p(out.ctypes.data)),
           "tfhe_pool2d_eval_plain")
     return out[0] if one else out
+
+
+def lut_tables_info(luts, q: int, inner: int = 1, B: int = 1):
+    """(classes[T], per_class[3], bootstraps) of a batch of B ciphertexts under luts[T, q] and `inner`: ciphertext i
+    uses table (i // inner) % T; class 0 negacyclic, 1 periodic, 2 arbitrary, each table classified on its own
+    (tfhe_lut_tables_info; no GPU)."""
+    t = np.ascontiguousarray(luts, dtype=np.uint64)
+    if t.ndim != 2 or t.shape[1] != q:
+        raise ValueError(f"lut_tables_info: tables must have shape (T, {q}), got {t.shape}")
+    classes = np.zeros(t.shape[0], dtype=np.uint8)
+    per = (SZ * 3)()
+    boots = U64()
+    check(lib().tfhe_lut_tables_info(q, C.c_void_p(t.ctypes.data), t.shape[0], inner, B,
+                                     C.c_void_p(classes.ctypes.data), per, C.byref(boots)), "tfhe_lut_tables_info")
+    return classes, (per[0], per[1], per[2]), boots.value
+
+
+def lut_classes(luts, q: int):
+    """The class of each table of luts[T, q] (0 negacyclic, 1 periodic, 2 arbitrary), as EvalFuncTables and the
+    layers with one table per channel classify them (no GPU)."""
+    return lut_tables_info(luts, q)[0]
 
 
 def max_table(q: int, negacyclic: bool = False):

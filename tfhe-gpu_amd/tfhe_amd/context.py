@@ -271,6 +271,14 @@ class BinFHEContextHIP:
               "tfhe_ciphertext_mul_matrix")
         return out
 
+    @staticmethod
+    def _layer_lut(who, lut, qq, channels):
+        """A layer's table argument: (q,) one shared table, or (channels, q) one per channel -> (array, tabled)."""
+        lut = _u64(lut)
+        if lut.shape != (qq,) and lut.shape != (channels, qq):
+            raise ValueError(f"{who}: LUT must have shape ({qq},) or ({channels}, {qq}), got {lut.shape}")
+        return np.ascontiguousarray(lut), lut.ndim == 2
+
     # -- vector BinFHEContext surface --
     def _batch(self, ct, what="ciphertexts"):
         ct = _rows(ct, self.params.n + 1, what)
@@ -296,6 +304,19 @@ class BinFHEContextHIP:
         out = np.empty((B, self.params.n + 1), dtype=np.uint64)
         self._check(self._L.tfhe_eval_func(self._h, B, ct.ravel(), qq, lut.ravel(), int(lut.ndim == 2),
                                    out.ravel()), "tfhe_eval_func")
+        return out
+
+    def EvalFuncTables(self, ct, luts, inner=1, q=None):
+        """One table per channel: ct[B, n+1], luts[T, q]; ciphertext i uses table (i // inner) % T, every table
+        classified on its own, each result bit for bit EvalFunc's with that table shared (tfhe_eval_func_tables)."""
+        ct, B = self._batch(ct, "EvalFuncTables")
+        luts = _u64(luts)
+        qq = q or self.params.q
+        if luts.ndim != 2 or luts.shape[0] == 0 or luts.shape[1] != qq:
+            raise ValueError(f"EvalFuncTables: tables must have shape (T, {qq}), got {luts.shape}")
+        out = np.empty((B, self.params.n + 1), dtype=np.uint64)
+        self._check(self._L.tfhe_eval_func_tables(self._h, B, ct.ravel(), qq, luts.ravel(), luts.shape[0], inner,
+                                                  out.ravel()), "tfhe_eval_func_tables")
         return out
 
     def EvalFloor(self, ct, mod, roundbits=0):
@@ -381,9 +402,7 @@ class BinFHEContextHIP:
         K, cols = m.shape
         if x.ndim != 3 or x.shape[0] == 0 or x.shape[1] != K or x.shape[2] != w:
             raise ValueError(f"EvalDense: expected shape (instances, {K}, {w}), got {x.shape}")
-        lut = _u64(lut)
-        if lut.shape != (qq,):
-            raise ValueError(f"EvalDense: LUT must have shape ({qq},), got {lut.shape}")
+        lut, tabled = self._layer_lut("EvalDense", lut, qq, cols)
         b = None
         if bias is not None:
             b = _u64(bias)
@@ -391,14 +410,27 @@ class BinFHEContextHIP:
                 raise ValueError(f"EvalDense: bias must have shape ({cols},), got {b.shape}")
         x = np.ascontiguousarray(x)
         out = np.empty((x.shape[0], cols, w), dtype=np.uint64)
-        self._check(self._L.tfhe_eval_dense(self._h, x.shape[0], K, x.ravel(), cols, m.ravel(),
-                                            C.c_void_p(b.ctypes.data if b is not None else None), qq, lut, out.ravel()),
-                    "tfhe_eval_dense")
+        bp = C.c_void_p(b.ctypes.data if b is not None else None)
+        if tabled:
+            self._check(self._L.tfhe_eval_dense_tables(self._h, x.shape[0], K, x.ravel(), cols, m.ravel(), bp, qq,
+                                                       lut.ravel(), cols, out.ravel()), "tfhe_eval_dense_tables")
+        else:
+            self._check(self._L.tfhe_eval_dense(self._h, x.shape[0], K, x.ravel(), cols, m.ravel(), bp, qq, lut,
+                                                out.ravel()), "tfhe_eval_dense")
         return out[0] if one else out
 
-    def EvalDenseDevice(self, instances, K, d_ct, cols, d_matrix, d_lut, d_out, d_bias=0, q=None, stream=0):
+    def EvalDenseDevice(self, instances, K, d_ct, cols, d_matrix, d_lut, d_out, d_bias=0, q=None, stream=0, num_luts=1):
         """d_ct[instances][K][n+1], d_matrix[K][cols] int64, d_lut[q], d_bias[cols] or 0 -> d_out[instances][cols][n+1],
-        device pointers."""
+        device pointers.  num_luts > 1: d_lut[num_luts = cols][q], one table per column."""
+        if num_luts < 1:
+            raise ValueError(f"EvalDenseDevice: num_luts must be at least 1, got {num_luts}")
+        if num_luts > 1:
+            self._check(self._L.tfhe_eval_dense_tables_device(self._h, instances, K, C.c_void_p(d_ct), cols,
+                                                              C.c_void_p(d_matrix), C.c_void_p(d_bias),
+                                                              q or self.params.q, C.c_void_p(d_lut), num_luts,
+                                                              C.c_void_p(d_out), C.c_void_p(stream)),
+                        "tfhe_eval_dense_tables_device")
+            return
         self._check(self._L.tfhe_eval_dense_device(self._h, instances, K, C.c_void_p(d_ct), cols, C.c_void_p(d_matrix),
                                                    C.c_void_p(d_bias), q or self.params.q, C.c_void_p(d_lut),
                                                    C.c_void_p(d_out), C.c_void_p(stream)), "tfhe_eval_dense_device")
@@ -437,9 +469,7 @@ class BinFHEContextHIP:
             oh, ow, _ = conv2d_shape(desc)  # the descriptor's own rules, on the host; the message names the field
         except TfheError as e:
             raise ValueError(f"EvalConv2d: {e}") from None
-        lut = _u64(lut)
-        if lut.shape != (qq,):
-            raise ValueError(f"EvalConv2d: LUT must have shape ({qq},), got {lut.shape}")
+        lut, tabled = self._layer_lut("EvalConv2d", lut, qq, W.shape[0])
         b = None
         if bias is not None:
             b = _u64(bias)
@@ -447,14 +477,28 @@ class BinFHEContextHIP:
                 raise ValueError(f"EvalConv2d: bias must have shape ({W.shape[0]},), got {b.shape}")
         x = np.ascontiguousarray(x)
         out = np.empty((x.shape[0], W.shape[0], oh, ow, w), dtype=np.uint64)
-        self._check(self._L.tfhe_eval_conv2d(self._h, C.byref(desc), x.shape[0], x.ravel(), W.ravel(),
-                                             C.c_void_p(b.ctypes.data if b is not None else None), qq, lut, out.ravel()),
-                    "tfhe_eval_conv2d")
+        bp = C.c_void_p(b.ctypes.data if b is not None else None)
+        if tabled:
+            self._check(self._L.tfhe_eval_conv2d_tables(self._h, C.byref(desc), x.shape[0], x.ravel(), W.ravel(), bp, qq,
+                                                        lut.ravel(), W.shape[0], out.ravel()), "tfhe_eval_conv2d_tables")
+        else:
+            self._check(self._L.tfhe_eval_conv2d(self._h, C.byref(desc), x.shape[0], x.ravel(), W.ravel(), bp, qq, lut,
+                                                 out.ravel()), "tfhe_eval_conv2d")
         return out[0] if one else out
 
-    def EvalConv2dDevice(self, desc, instances, d_ct, d_weight, d_lut, d_out, d_bias=0, q=None, stream=0):
+    def EvalConv2dDevice(self, desc, instances, d_ct, d_weight, d_lut, d_out, d_bias=0, q=None, stream=0, num_luts=1):
         """desc: tfhe_amd.Conv2d; d_ct[instances][c_in][h][w][n+1], d_weight[c_out][c_in/groups][kh][kw] int64, d_lut[q],
-        d_bias[c_out] or 0 -> d_out[instances][c_out][oh][ow][n+1], device pointers."""
+        d_bias[c_out] or 0 -> d_out[instances][c_out][oh][ow][n+1], device pointers.  num_luts > 1:
+        d_lut[num_luts = c_out][q], one table per output plane."""
+        if num_luts < 1:
+            raise ValueError(f"EvalConv2dDevice: num_luts must be at least 1, got {num_luts}")
+        if num_luts > 1:
+            self._check(self._L.tfhe_eval_conv2d_tables_device(self._h, C.byref(desc), instances, C.c_void_p(d_ct),
+                                                               C.c_void_p(d_weight), C.c_void_p(d_bias),
+                                                               q or self.params.q, C.c_void_p(d_lut), num_luts,
+                                                               C.c_void_p(d_out), C.c_void_p(stream)),
+                        "tfhe_eval_conv2d_tables_device")
+            return
         self._check(self._L.tfhe_eval_conv2d_device(self._h, C.byref(desc), instances, C.c_void_p(d_ct),
                                                     C.c_void_p(d_weight), C.c_void_p(d_bias), q or self.params.q,
                                                     C.c_void_p(d_lut), C.c_void_p(d_out), C.c_void_p(stream)),
@@ -491,13 +535,15 @@ class BinFHEContextHIP:
             oh, ow, _, _ = pool2d_shape(desc)  # the descriptor's own rules, on the host; the message names the field
         except TfheError as e:
             raise ValueError(f"EvalPool2d: {e}") from None
-        lut = _u64(lut)
-        if lut.shape != (qq,):
-            raise ValueError(f"EvalPool2d: LUT must have shape ({qq},), got {lut.shape}")
+        lut, tabled = self._layer_lut("EvalPool2d", lut, qq, x.shape[1])
         x = np.ascontiguousarray(x)
         out = np.empty((x.shape[0], x.shape[1], oh, ow, w), dtype=np.uint64)
-        self._check(self._L.tfhe_eval_pool2d(self._h, C.byref(desc), x.shape[0], x.ravel(), qq, lut, out.ravel()),
-                    "tfhe_eval_pool2d")
+        if tabled:
+            self._check(self._L.tfhe_eval_pool2d_tables(self._h, C.byref(desc), x.shape[0], x.ravel(), qq, lut.ravel(),
+                                                        x.shape[1], out.ravel()), "tfhe_eval_pool2d_tables")
+        else:
+            self._check(self._L.tfhe_eval_pool2d(self._h, C.byref(desc), x.shape[0], x.ravel(), qq, lut, out.ravel()),
+                        "tfhe_eval_pool2d")
         return out[0] if one else out
 
     def EvalMaxPool2d(self, cts, kernel, stride=None, padding=0, negacyclic=False, q=None):
@@ -505,9 +551,17 @@ class BinFHEContextHIP:
         pair and differences in (-q/2, q/2); negacyclic=True takes one and differences in (-q/4, q/4)."""
         return self.EvalPool2d(cts, max_table(q or self.params.q, negacyclic), kernel, stride, padding, q)
 
-    def EvalPool2dDevice(self, desc, instances, d_ct, d_lut, d_out, q=None, stream=0):
+    def EvalPool2dDevice(self, desc, instances, d_ct, d_lut, d_out, q=None, stream=0, num_luts=1):
         """desc: tfhe_amd.Pool2d; d_ct[instances][c][h][w][n+1], d_lut[q] -> d_out[instances][c][oh][ow][n+1], device
-        pointers; no input word is written."""
+        pointers; no input word is written.  num_luts > 1: d_lut[num_luts = c][q], one table per plane."""
+        if num_luts < 1:
+            raise ValueError(f"EvalPool2dDevice: num_luts must be at least 1, got {num_luts}")
+        if num_luts > 1:
+            self._check(self._L.tfhe_eval_pool2d_tables_device(self._h, C.byref(desc), instances, C.c_void_p(d_ct),
+                                                               q or self.params.q, C.c_void_p(d_lut), num_luts,
+                                                               C.c_void_p(d_out), C.c_void_p(stream)),
+                        "tfhe_eval_pool2d_tables_device")
+            return
         self._check(self._L.tfhe_eval_pool2d_device(self._h, C.byref(desc), instances, C.c_void_p(d_ct),
                                                     q or self.params.q, C.c_void_p(d_lut), C.c_void_p(d_out),
                                                     C.c_void_p(stream)),
@@ -524,6 +578,13 @@ class BinFHEContextHIP:
         self._check(self._L.tfhe_eval_func_device(self._h, B, C.c_void_p(d_ct), q or self.params.q, C.c_void_p(d_lut),
                                           int(per_ct_lut), C.c_void_p(d_out), C.c_void_p(stream)),
               "tfhe_eval_func_device")
+
+    def EvalFuncTablesDevice(self, B, d_ct, d_luts, num_luts, d_out, inner=1, q=None, stream=0):
+        """d_ct[B][n+1], d_luts[num_luts][q] -> d_out[B][n+1], device pointers; ciphertext i uses table
+        (i // inner) % num_luts."""
+        self._check(self._L.tfhe_eval_func_tables_device(self._h, B, C.c_void_p(d_ct), q or self.params.q,
+                                                         C.c_void_p(d_luts), num_luts, inner, C.c_void_p(d_out),
+                                                         C.c_void_p(stream)), "tfhe_eval_func_tables_device")
 
     def EvalFloorDevice(self, B, d_ct, mod, d_out, roundbits=0, stream=0):
         self._check(self._L.tfhe_eval_floor_device(self._h, B, C.c_void_p(d_ct), mod, roundbits, C.c_void_p(d_out),
