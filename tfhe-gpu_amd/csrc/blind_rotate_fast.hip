@@ -23,7 +23,7 @@ namespace {
 
 constexpr uint32_t FN = 1024;
 // the fast key buffer: [four-wavefront kernel tables (blind_rotate_fast4.hip)][key rows]
-constexpr uint32_t T4W = 5416, TB_WORDS = T4W;
+constexpr uint32_t T4W = 6864, TB_WORDS = T4W;
 
 struct FastConst {  // = f4::FastConst (blind_rotate_fast4.hip)
     int32_t Q, nQ, qinv, rM;  // rM = R mod Q (centred): smul(x, rM) reduces x
@@ -87,11 +87,12 @@ size_t bsk_fast_bytes(const BRParams& P) { return ((size_t)P.n * 2 * P.dG2 * 2 *
 namespace {
 // TFHE_FAST_VARIANT / tfhe_set_kernel_variant select the build of the four-wavefront kernel:
 // 60 = default (batches from the pair_min launch setting on take 70's kernel); 70 (two ciphertexts per
-// wavefront: the pair instance at every batch size) and 86 (four per workgroup) are kept as
+// wavefront: the pair instance at every batch size; 71: the same with fused radix-4 groups; 61: the default
+// one-ciphertext build with the inverse's fused groups) and 86 (four per workgroup) are kept as
 // cross-checks of the multi-ciphertext paths (tests/test_gpu_kernel_variants.py).  The other
 // round-1/2 builds were removed in round 3.
 constexpr int kDefaultVariant = 60;
-bool known_variant(int v) { return v == 60 || v == 70 || v == 86; }
+bool known_variant(int v) { return v == 60 || v == 61 || v == 70 || v == 71 || v == 86; }
 std::atomic<int> g_variant{-1};
 int fast_variant() {
     int v = g_variant.load(std::memory_order_relaxed);

@@ -27,6 +27,11 @@
 //    (SGPRs), passes 1-3 come from LDS (ds_read_b128).  Pass 0 of a digit polynomial (7-bit
 //    inputs) reads all its products from three 128-entry LDS tables.
 //  * Inverse passes on L4 and L2 reduce their second-stage sums (tools/bounds_fast4.py).
+//  * FU (fused radix-4 groups): the two inputs that meet in a group's second stage are combined as a 64-bit
+//    sum of two products and reduced once (fwd4f / inv4f: 17 VALU per group instead of 20, RED groups 20
+//    instead of 26).  Needs the products p21 = w2 w1, n31 = -w3 w1 beside each twiddle triple; passes 1-3 then
+//    read ONE table both ways (the inverse's block c is the forward's block m - 1 - c negated, the signs taken
+//    up by the order of the differences), which makes room for the two extra words in the same LDS area.
 #include "device_math.hpp"
 #include "kernels.hpp"
 
@@ -40,10 +45,20 @@ constexpr int TPC = 256;
 //   pass p >= 1 block c (m = 4^p): [psi[m+c], psi[2m+2c], psi[2m+2c+1], 0]; pass 0 = block 0 of m = 1
 constexpr uint32_t P0F = 0, P1F = 4, P2F = 20, P3F = 84, P4F = 340, PF_END = 1364;
 constexpr uint32_t P0I = PF_END, P1I = P0I + P1F, P4I = P0I + P4F;
-constexpr uint32_t T4_MONO = 2 * PF_END, T4_T1 = T4_MONO + 2 * FN, T4_T23 = T4_T1 + 128, T4_T2131 = T4_T23 + 256,
-                   T4_WORDS = T4_T2131 + 256;
+constexpr uint32_t T4_MONO = 2 * PF_END, T4_T1 = T4_MONO + 2 * FN, T4_T23 = T4_T1 + 128, T4_T2131 = T4_T23 + 256;
+// fused groups (FU): FU0 = pass 0's [p21, n31] forward and [p12, n13] inverse; FUL = passes 1-3, the forward
+// blocks with p21 as their fourth word (84 blocks; pass 3's in lane order) and then n31 of every block; FU4 =
+// pass 4, per lane [p21, n31] forward and [p12, n13] inverse
+constexpr uint32_t FUL_BLK = P4F - P1F, FUL_WORDS = FUL_BLK + FUL_BLK / 4;
+constexpr uint32_t T4_FU0 = T4_T2131 + 256, T4_FUL = T4_FU0 + 4, T4_FU4 = T4_FUL + FUL_WORDS, T4_WORDS = T4_FU4 + 4 * 256;
+// FU bits: fused forward pass 0 (the untabled one), inverse passes L4 - L2 (which puts the shared table into LDS),
+// forward pass 4, inverse L5, inverse L1, forward passes 1-3 (shared table only: the plain forward pass reads it
+// too, the plain inverse cannot)
+enum : int { FU_F0 = 1, FU_L = 2, FU_F4 = 4, FU_I5 = 8, FU_I1 = 16, FU_LF = 32, FU_ALL = 63 };
 // LDS (words): pass 1-3 twiddles (fwd, inv), monomials, 4 local regions, 2 cross areas
 constexpr uint32_t L_TW = 0, L_TWI = P4F - P1F, L_MONO = 2 * L_TWI;  // passes 1-3 (fwd, inv)
+constexpr uint32_t L_N31 = L_TW + FUL_BLK;  // FU_L: the shared table's n31 words in place of the inverse table
+static_assert(FUL_WORDS <= L_MONO, "the shared table fits the two tables' area");
 // then, for P polynomials per wavefront: 4 local regions of P x LP words, 2 cross areas of P x XP
 // T1[d + 64] = d psi[1] mod Q for digits d in [-64, 64): pass 0's first stage on a digit polynomial
 // T23[d] = (d psi[2], d psi[3]), T2131[d] = (d psi[2] psi[1], d psi[3] psi[1]): the rest of pass 0
@@ -183,6 +198,29 @@ __device__ __forceinline__ void inv4(int32_t (&x)[4], int32_t w1, int32_t w2, in
     bfly_gs<RED>(x[1], x[3], w1, K);
 }
 
+// Fused radix-4 groups: the second stage's two products as one 64-bit sum (mac64: one multiply, one
+// v_mad_i64_i32), reduced once.  p21 = w2 w1, n31 = -w3 w1 (centred Montgomery forms).
+__device__ __forceinline__ void fwd4f(int32_t (&x)[4], int32_t w1, int32_t w2, int32_t w3, int32_t p21, int32_t n31,
+                                      const FastConst& K) {
+    const int32_t t = smul(x[2], w1, K), a = x[0] + t, b = x[0] - t;
+    const int32_t c = sredc(mac64(x[3], p21, (int64_t)x[1] * w2), K);
+    const int32_t d = sredc(mac64(x[3], n31, (int64_t)x[1] * w3), K);
+    x[0] = a + c, x[1] = a - c, x[2] = b + d, x[3] = b - d;
+}
+// y1 = e wa + f wb, y3 = e pa + f pb, y2 = (s0 - s2) w1 with e = x0 - x1, f = x2 - x3.  Own twiddles: (wa, wb, pa,
+// pb) = (w2, w3, w1 w2, -w1 w3).  MIR: the twiddles are the forward table's block m - 1 - c, (w1', w3', w2', n31',
+// p21'): the inverse's are their negatives, so every difference is taken the other way round.
+template <bool RED, bool MIR>
+__device__ __forceinline__ void inv4f(int32_t (&x)[4], int32_t w1, int32_t wa, int32_t wb, int32_t pa, int32_t pb,
+                                      const FastConst& K) {
+    const int32_t e = MIR ? x[1] - x[0] : x[0] - x[1], f = MIR ? x[3] - x[2] : x[2] - x[3];
+    const int32_t s0 = x[0] + x[1], s2 = x[2] + x[3];
+    x[1] = sredc(mac64(f, wb, (int64_t)e * wa), K);
+    x[3] = sredc(mac64(f, pb, (int64_t)e * pa), K);
+    x[2] = smul(MIR ? s2 - s0 : s0 - s2, w1, K);
+    x[0] = RED ? smul(s0 + s2, K.rM, K) : s0 + s2;
+}
+
 // ---- LDS traffic (inline asm: counted lgkmcnt waits, addtid stores) ----
 // one polynomial's 4 registers as 4 lane-contiguous rows at M0 + OFF
 template <int A, int B, uint32_t OFF>
@@ -214,6 +252,30 @@ template <uint32_t OFF>
 __device__ __forceinline__ void tw_load(v4i& w, uint32_t addr, const int32_t* lds) {
     asm volatile("ds_read_b128 %0, %1 offset:%3" : "=&v"(w) : "v"(addr), "s"(lds), "i"(OFF * 4) : "memory");
 }
+template <uint32_t OFF>
+__device__ __forceinline__ void tw_load1(int32_t& w, uint32_t addr, const int32_t* lds) {
+    asm volatile("ds_read_b32 %0, %1 offset:%3" : "=&v"(w) : "v"(addr), "s"(lds), "i"(OFF * 4) : "memory");
+}
+// The shared table's addresses (FU_L): volatile, so that they are formed where they are used, once per pass.
+// Left to the compiler they are hoisted out of the round loop as nine more per-lane constants, which it spills.
+template <uint32_t M>
+__device__ __forceinline__ uint32_t tw_mirror(uint32_t t) {  // block M - 1 - c of a pass of M blocks (bytes)
+    uint32_t r;
+    asm volatile("v_sub_u32_e32 %0, %1, %2" : "=v"(r) : "i"((M - 1) * 16), "v"(t));
+    return r;
+}
+__device__ __forceinline__ uint32_t tw_side(uint32_t t) {  // a block's word of the n31 array (bytes)
+    uint32_t r;
+    asm volatile("v_lshrrev_b32_e32 %0, 2, %1" : "=v"(r) : "v"(t));
+    return r;
+}
+template <int N>
+__device__ __forceinline__ void lds_wait(int32_t (&x)[4], v4i& w, int32_t& w5) {
+    asm volatile("s_waitcnt lgkmcnt(%6)"
+                 : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(w), "+v"(w5)
+                 : "i"(N)
+                 : "memory");
+}
 template <int N>
 __device__ __forceinline__ void lds_wait(int32_t (&x)[4]) {
     asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]) : "i"(N) : "memory");
@@ -238,6 +300,10 @@ struct LaneCtx {
     uint32_t t1, t2, t3, t4;                          // pass 1 / 2 / 3 / 4 twiddle block addresses (bytes)
     int32_t w0f[3], w0i[3];                           // pass 0 (uniform)
     v4i w4f, w4i;                                     // pass 4 (per lane)
+    // fused groups: pass 0's (p21, n31) / (p12, n13) (uniform); pass 4's ride in the fourth words of w4f / w4i
+    // (forward p21 in w4f.w; w4i.w = the inverse's p12, or the forward's n31 where the L5 pass is not fused)
+    int32_t p0f[2], p0i[2];
+    int32_t x4f, x4i;                                 // FU_F4 and FU_I5: forward n31, inverse n13 (per lane)
 };
 
 // ---- transforms of P polynomials (P = 2 per ciphertext of the wavefront) ----
@@ -268,11 +334,26 @@ constexpr int tail_wait() { return 4 * (P - 1 - p); }
 // P4L: pass-4 twiddles from LDS (L_P4F) instead of registers.
 // PRE: one cross area only, so every wavefront must have finished reading its previous
 // contents before anyone stores (a plain barrier: those reads completed long ago)
-template <uint32_t XA, int P, int EXP = 0, int SMALL = 0, bool PRE = false, bool P4L = false>
+template <uint32_t XA, int P, int EXP = 0, int SMALL = 0, bool PRE = false, bool P4L = false, int FU = 0>
 __device__ __forceinline__ void ntt_fwd(int32_t (&X)[P][4], const int32_t* lds, const LaneCtx& C, const FastConst& K) {
     if constexpr ((EXP & 8) != 0) return;
     constexpr int W = 4 * (P - 1);
+    static_assert(!(P4L && (FU & FU_F4)), "fused pass 4 takes its twiddles from registers");
+    static_assert(!(FU & FU_LF) || (FU & FU_L), "fused forward passes 1-3 need the shared table");
     v4i w;
+    int32_t w5 = 0;  // FU_L: n31 of the pass's block
+    // FU_L: the pass's twiddle block and its n31 word (side array: word index = block index)
+#define TW_LOAD(OFF, T)                                                  \
+    tw_load<L_TW + OFF>(w, T, lds);                                      \
+    if constexpr ((FU & FU_LF) != 0) tw_load1<L_N31 + OFF / 4>(w5, tw_side(T), lds);
+#define FWD_PASS(p)                                                                         \
+    if constexpr ((FU & FU_LF) != 0) {                                                      \
+        if constexpr (p == 0) lds_wait<W>(X[0], w, w5); else lds_wait<W>(X[p]);             \
+        fwd4f(X[p], w.x, w.y, w.z, w.w, w5, K);                                             \
+    } else {                                                                                \
+        if constexpr (p == 0) lds_wait<W>(X[0], w); else lds_wait<W>(X[p]);                 \
+        fwd4(X[p], w.x, w.y, w.z, K);                                                       \
+    }
     // pass 0 (L1), exchange 1 -> 2
     if constexpr (SMALL == 2) {
         const int32_t* t1 = lds + L_T1 + 64;
@@ -293,24 +374,23 @@ __device__ __forceinline__ void ntt_fwd(int32_t (&X)[P][4], const int32_t* lds, 
               X[p][0] = a0 + v[p][0]; X[p][2] = a0 - v[p][0]; X[p][1] = a1 + v[p][1]; X[p][3] = a1 - v[p][1];
               bfly_ct(X[p][0], X[p][1], C.w0f[1], K); bfly_ct(X[p][2], X[p][3], C.w0f[2], K);
               store_rows<1, 2, p * LP>(X[p], C.m_loc, lds);)
+    } else if constexpr ((FU & FU_F0) != 0) {
+        FOR_P(fwd4f(X[p], C.w0f[0], C.w0f[1], C.w0f[2], C.p0f[0], C.p0f[1], K); store_rows<1, 2, p * LP>(X[p], C.m_loc, lds);)
     } else {
         FOR_P(fwd4(X[p], C.w0f[0], C.w0f[1], C.w0f[2], K); store_rows<1, 2, p * LP>(X[p], C.m_loc, lds);)
     }
-    tw_load<L_TW>(w, C.t1, lds);
+    TW_LOAD(0, C.t1)
     FOR_P(gather_rows<1, 2, p * LP>(X[p], C.g12, lds);)
     // pass 1 (L2), exchange 2 -> 3
-    FOR_P(if constexpr (p == 0) lds_wait<W>(X[0], w); else lds_wait<W>(X[p]);
-          fwd4(X[p], w.x, w.y, w.z, K); store_rows<2, 3, p * LP>(X[p], C.m_loc, lds);)
-    tw_load<L_TW + 16>(w, C.t2, lds);
+    FOR_P(FWD_PASS(p) store_rows<2, 3, p * LP>(X[p], C.m_loc, lds);)
+    TW_LOAD(16, C.t2)
     FOR_P(gather_rows<2, 3, p * LP>(X[p], C.g23, lds);)
     // pass 2 (L3), exchange 3 -> 4
-    FOR_P(if constexpr (p == 0) lds_wait<W>(X[0], w); else lds_wait<W>(X[p]);
-          fwd4(X[p], w.x, w.y, w.z, K); store_rows<3, 4, p * LP>(X[p], C.m_loc, lds);)
-    tw_load<L_TW + 80>(w, C.t3, lds);
+    FOR_P(FWD_PASS(p) store_rows<3, 4, p * LP>(X[p], C.m_loc, lds);)
+    TW_LOAD(80, C.t3)
     FOR_P(gather_rows<3, 4, p * LP>(X[p], C.g34, lds);)
     // pass 3 (L4), cross exchange 4 -> 5
-    FOR_P(if constexpr (p == 0) lds_wait<W>(X[0], w); else lds_wait<W>(X[p]);
-          fwd4(X[p], w.x, w.y, w.z, K);
+    FOR_P(FWD_PASS(p)
           if constexpr (PRE && p == 0) __builtin_amdgcn_s_barrier();
           store_rows<4, 5, XA + p * XP>(X[p], C.m45, lds);)
     if constexpr (!(EXP & 1)) lds_drain_barrier();
@@ -320,45 +400,71 @@ __device__ __forceinline__ void ntt_fwd(int32_t (&X)[P][4], const int32_t* lds, 
     if constexpr (P4L) {
         FOR_P(if constexpr (p == 0) lds_wait<tail_wait<P, 0>()>(X[0], w); else lds_wait<tail_wait<P, p>()>(X[p]);
               fwd4(X[p], w.x, w.y, w.z, K);)
+    } else if constexpr ((FU & FU_F4) != 0) {
+        FOR_P(lds_wait<tail_wait<P, p>()>(X[p]);
+              fwd4f(X[p], C.w4f.x, C.w4f.y, C.w4f.z, C.w4f.w, (FU & FU_I5) ? C.x4f : C.w4i.w, K);)
     } else {
         FOR_P(lds_wait<tail_wait<P, p>()>(X[p]); fwd4(X[p], C.w4f.x, C.w4f.y, C.w4f.z, K);)
     }
+#undef TW_LOAD
+#undef FWD_PASS
 }
 
 // inverse (N^-1 folded into the keys), L5 -> L1
-template <uint32_t XA, int P, int EXP = 0, bool PRE = false>
+template <uint32_t XA, int P, int EXP = 0, bool PRE = false, int FU = 0>
 __device__ __forceinline__ void ntt_inv(int32_t (&X)[P][4], const int32_t* lds, const LaneCtx& C, const FastConst& K) {
     if constexpr ((EXP & 8) != 0) return;
     constexpr int W = 4 * (P - 1);
     v4i w;
+    int32_t w5 = 0;
+    // the pass's twiddles: the inverse table's block c, or (FU_L) the shared table's block M - 1 - c and its n31
+#define TWI_LOAD(OFF, M, T)                                                  \
+    if constexpr ((FU & FU_L) != 0) {                                        \
+        const uint32_t tm = tw_mirror<M>(T);                                 \
+        tw_load<L_TW + OFF>(w, tm, lds);                                     \
+        tw_load1<L_N31 + OFF / 4>(w5, tw_side(tm), lds);                     \
+    } else {                                                                 \
+        tw_load<L_TWI + OFF>(w, T, lds);                                     \
+    }
+#define INV_PASS(p, RED)                                                                    \
+    if constexpr ((FU & FU_L) != 0) {                                                       \
+        if constexpr (p == 0) lds_wait<W>(X[0], w, w5); else lds_wait<W>(X[p]);             \
+        inv4f<RED, true>(X[p], w.x, w.z, w.y, w5, w.w, K);                                  \
+    } else {                                                                                \
+        if constexpr (p == 0) lds_wait<W>(X[0], w); else lds_wait<W>(X[p]);                 \
+        inv4<RED>(X[p], w.x, w.y, w.z, K);                                                  \
+    }
     // (b0 b1) (L5), cross exchange 5 -> 4
-    FOR_P(inv4<false>(X[p], C.w4i.x, C.w4i.y, C.w4i.z, K); if constexpr (PRE && p == 0) __builtin_amdgcn_s_barrier();
+    FOR_P(if constexpr ((FU & FU_I5) != 0) inv4f<false, false>(X[p], C.w4i.x, C.w4i.y, C.w4i.z, C.w4i.w, C.x4i, K);
+          else inv4<false>(X[p], C.w4i.x, C.w4i.y, C.w4i.z, K);
+          if constexpr (PRE && p == 0) __builtin_amdgcn_s_barrier();
           store_rows<5, 4, XA + p * XP>(X[p], C.m54, lds);)
     if constexpr (!(EXP & 1)) lds_drain_barrier();
-    tw_load<L_TWI + 80>(w, C.t3, lds);
+    TWI_LOAD(80, 64, C.t3)
     FOR_P(gather_rows<5, 4, XA + p * XP>(X[p], C.g54, lds);)
     // (b2 b3) (L4, reduced), exchange 4 -> 3
-    FOR_P(if constexpr (p == 0) lds_wait<W>(X[0], w); else lds_wait<W>(X[p]);
-          inv4<true>(X[p], w.x, w.y, w.z, K);
-          store_rows<4, 3, p * LP>(X[p], C.m_loc, lds);)
-    tw_load<L_TWI + 16>(w, C.t2, lds);
+    FOR_P(INV_PASS(p, true) store_rows<4, 3, p * LP>(X[p], C.m_loc, lds);)
+    TWI_LOAD(16, 16, C.t2)
     FOR_P(gather_rows<4, 3, p * LP>(X[p], C.g43, lds);)
     // (b4 b5) (L3), exchange 3 -> 2
-    FOR_P(if constexpr (p == 0) lds_wait<W>(X[0], w); else lds_wait<W>(X[p]);
-          inv4<false>(X[p], w.x, w.y, w.z, K); store_rows<3, 2, p * LP>(X[p], C.m_loc, lds);)
-    tw_load<L_TWI>(w, C.t1, lds);
+    FOR_P(INV_PASS(p, false) store_rows<3, 2, p * LP>(X[p], C.m_loc, lds);)
+    TWI_LOAD(0, 4, C.t1)
     FOR_P(gather_rows<3, 2, p * LP>(X[p], C.g32, lds);)
     // (b6 b7) (L2, reduced), exchange 2 -> 1
-    FOR_P(if constexpr (p == 0) lds_wait<W>(X[0], w); else lds_wait<W>(X[p]);
-          inv4<true>(X[p], w.x, w.y, w.z, K); store_rows<2, 1, p * LP>(X[p], C.m_loc, lds);)
+    FOR_P(INV_PASS(p, true) store_rows<2, 1, p * LP>(X[p], C.m_loc, lds);)
     FOR_P(gather_rows<2, 1, p * LP>(X[p], C.g21, lds);)
     // (b8 b9) (L1)
-    FOR_P(lds_wait<tail_wait<P, p>()>(X[p]); inv4<false>(X[p], C.w0i[0], C.w0i[1], C.w0i[2], K);)
+    FOR_P(lds_wait<tail_wait<P, p>()>(X[p]);
+          if constexpr ((FU & FU_I1) != 0) inv4f<false, false>(X[p], C.w0i[0], C.w0i[1], C.w0i[2], C.p0i[0], C.p0i[1], K);
+          else inv4<false>(X[p], C.w0i[0], C.w0i[1], C.w0i[2], K);)
+#undef TWI_LOAD
+#undef INV_PASS
 }
 
 // NCT ciphertexts per wavefront (the same slots of each): every key row loaded feeds NCT
 // ciphertexts, halving the vector-memory traffic per bootstrap at NCT = 2.
 // RING: key-ring depth in groups, 4 (above) or 2.
+// FU: which radix-4 passes run as fused groups (FU_* bits above)
 // OPT bit 0: T1 lookups in the digit transforms (bit 2: all of pass 0 from tables); bit 1: Barrett
 // accumulator update; bit 3: pass-4 forward twiddles from LDS
 // XB: cross-exchange areas (2: alternate, no barrier before the stores; 1: one area + a barrier)
@@ -378,7 +484,7 @@ __device__ __forceinline__ void ntt_inv(int32_t (&X)[P][4], const int32_t* lds, 
 // when THR = 0 and the top digit never wraps (the host checks); otherwise every digit is
 // transformed.  Pass 0's lookup tables hold digits in [-64, 64), so they need LOGG <= 7.
 template <int MINW, int NCT = 1, int EXP = 0, int OPT = 7, int XB = 2, int CTS = 1, int DIG = 4, int LOGG = 7,
-          int THR = 0, bool FOLD = true, bool FLAG = false, bool SPLIT = false, int RING = 4>
+          int THR = 0, bool FOLD = true, bool FLAG = false, bool SPLIT = false, int RING = 4, int FU = 0>
 __global__ void __launch_bounds__(TPC * (SPLIT ? 2 : CTS), MINW)
 k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __restrict__ tabs,
                      const int32_t* __restrict__ bsk, const uint64_t* __restrict__ a, uint64_t* __restrict__ acc_io,
@@ -402,7 +508,12 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
     const uint32_t tid = threadIdx.x % TPC;
     const uint32_t wg_ct = SPLIT ? blockIdx.x : blockIdx.x * CTS * NCT + cl;  // first ciphertext of this lane
     const uint32_t pol = SPLIT ? cl : 0;                                      // SPLIT: this group's polynomial
-    for (uint32_t k = threadIdx.x; k < L_TWI; k += TPC * GR) lds[L_TW + k] = tabs[P1F + k], lds[L_TWI + k] = tabs[P1I + k];
+    static_assert(!(FU & (FU_F4 | FU_I5)) || (OPT & 8) == 0, "fused pass 4 takes its twiddles from registers");
+    if constexpr ((FU & FU_L) != 0) {
+        for (uint32_t k = threadIdx.x; k < FUL_WORDS; k += TPC * GR) lds[L_TW + k] = tabs[T4_FUL + k];
+    } else {
+        for (uint32_t k = threadIdx.x; k < L_TWI; k += TPC * GR) lds[L_TW + k] = tabs[P1F + k], lds[L_TWI + k] = tabs[P1I + k];
+    }
     for (uint32_t k = threadIdx.x; k < 2 * FN + 640; k += TPC * GR) lds[L_MONO + k] = tabs[T4_MONO + k];  // monomials, T1/T23/T2131
     if constexpr ((OPT & 8) != 0)
         for (uint32_t k = threadIdx.x; k < 4 * 256; k += TPC * GR) lds[L_P4F + k] = tabs[P4F + k];
@@ -422,11 +533,22 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
     C.m45 = ctb + st_wave<4, 5>(w) * 4, C.m54 = ctb + st_wave<5, 4>(w) * 4;
     C.t1 = (elem<2>(w, lane, 0) >> 8) * 16, C.t2 = (elem<3>(w, lane, 0) >> 6) * 16;
     C.t3 = (elem<4>(w, lane, 0) >> 4) * 16, C.t4 = tid * 16;
+    if constexpr ((FU & FU_L) != 0) C.t3 = lane * 16;  // the shared table's pass-3 blocks are in lane order
     const v4i* tv = reinterpret_cast<const v4i*>(tabs);
     if constexpr ((OPT & 8) == 0) C.w4f = tv[P4F / 4 + tid];
     C.w4i = tv[P4I / 4 + tid];
 #pragma unroll
     for (int k = 0; k < 3; ++k) C.w0f[k] = tabs[P0F + k], C.w0i[k] = tabs[P0I + k];
+    if constexpr ((FU & (FU_F0 | FU_I1)) != 0) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) C.p0f[k] = tabs[T4_FU0 + k], C.p0i[k] = tabs[T4_FU0 + 2 + k];
+    }
+    if constexpr ((FU & (FU_F4 | FU_I5)) != 0) {
+        const v4i x4 = tv[T4_FU4 / 4 + tid];  // [p21, n31] forward, [p12, n13] inverse
+        if constexpr ((FU & FU_F4) != 0) C.w4f.w = x4.x, C.x4f = x4.y;
+        if constexpr ((FU & FU_I5) != 0) C.w4i.w = x4.z, C.x4i = x4.w;
+        else C.w4i.w = x4.y;
+    }
 
     const uint32_t Qh = (uint32_t)K.Q >> 1;
     int32_t acc[NCT][NPOL][4];  // L1, centred canonical
@@ -457,7 +579,7 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
 #pragma unroll
                 for (int r = 0; r < 4; ++r) Cp[2 * q][r] = acc[q][0][r], Cp[2 * q + 1][r] = acc[q][NPOL - 1][r];
         }
-        ntt_fwd<XA1, P, EXP, 0, PRE, (OPT & 8) != 0>(Cp, lds, C, K);
+        ntt_fwd<XA1, P, EXP, 0, PRE, (OPT & 8) != 0, FU>(Cp, lds, C, K);
 #pragma unroll
         for (int p = 0; p < P; ++p)
 #pragma unroll
@@ -468,7 +590,7 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
     const __amdgpu_buffer_rsrc_t rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(bsk), 0, (int)(n * ROWB), 0x00020000);
     const uint32_t voff = tid * 16;  // 4 consecutive slots per lane
-    const uint32_t et = 2 * (__builtin_bitreverse32(tid) >> 24) + 1;  // slot 4t + r: e = 512 bitrev2(r) + et
+    const uint32_t et0 = 2 * (__builtin_bitreverse32(tid) >> 24) + 1;  // slot 4t + r: e = 512 bitrev2(r) + et
     const uint32_t amask = (1u << loga) - 1, ashift = 11 - loga;
 
     // group gi = (key k, column j) of digit l (FOLD, l = TOP: the C rows): rows 2l (poly 0), 2l + 1 (poly 1)
@@ -566,8 +688,8 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
             }
             __builtin_amdgcn_sched_barrier(0);
             constexpr int SM = LOGG > 7 ? 0 : (OPT & 4) ? 2 : (OPT & 1) ? 1 : 0;
-            if (l & 1) ntt_fwd<XA1, P, EXP, SM, PRE, (OPT & 8) != 0>(X, lds, C, K);
-            else ntt_fwd<XA0, P, EXP, SM, PRE, (OPT & 8) != 0>(X, lds, C, K);
+            if (l & 1) ntt_fwd<XA1, P, EXP, SM, PRE, (OPT & 8) != 0, FU>(X, lds, C, K);
+            else ntt_fwd<XA0, P, EXP, SM, PRE, (OPT & 8) != 0, FU>(X, lds, C, K);
             // next digit's rows (after the last, FOLD: the next round's C rows; the last round
             // re-fetches)
             const bool last = l + 1 == NT;
@@ -587,6 +709,13 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
 
         // S_j = A_0j * NTT(X^a' - 1) + A_1j * NTT(X^-a' - 1); rotated monomial table
         __builtin_amdgcn_sched_barrier(0);
+        uint32_t et = et0;
+        if constexpr ((FU & (FU_F4 | FU_I5)) != 0) {
+            // formed again from voff (= 16 tid) every round, which frees its register for pass 4's products
+            uint32_t br;
+            asm volatile("v_bfrev_b32_e32 %0, %1" : "=v"(br) : "v"(voff));
+            et = ((br >> 19) & 0x1FE) | 1;
+        }
         const char* mono = reinterpret_cast<const char*>(lds + L_MONO);
         int32_t S[P][4];
         if constexpr (SPLIT) {
@@ -652,7 +781,7 @@ k_blind_rotate_fast4(FastConst K, uint32_t n, uint32_t loga, const int32_t* __re
             issue(pw[0], noff, TOP, 0), issue(pw[1], noff, TOP, 1);
             __builtin_amdgcn_sched_barrier(0);
         }
-        ntt_inv<XA1, P, EXP, PRE>(S, lds, C, K);
+        ntt_inv<XA1, P, EXP, PRE, FU>(S, lds, C, K);
 #pragma unroll
         for (int q = 0; q < NCT; ++q)
 #pragma unroll
@@ -738,6 +867,23 @@ __global__ void k_pack_tables4(uint32_t Q, const uint32_t* __restrict__ psi, con
         out[T4_T23 + 2 * idx] = dmul(psi[2]), out[T4_T23 + 2 * idx + 1] = dmul(psi[3]);
         out[T4_T2131 + 2 * idx] = dmul(p21), out[T4_T2131 + 2 * idx + 1] = dmul(p31);
     }
+    // fused groups: p = w2 w1, n = -w3 w1 of block c of a pass with m blocks
+    auto pn = [Q, &mont](const uint32_t* t, uint32_t m, uint32_t c, bool neg) {
+        const uint32_t v = (uint32_t)((uint64_t)t[2 * m + 2 * c + (neg ? 1 : 0)] * t[m + c] % Q);
+        return mont(neg ? (v ? Q - v : 0) : v);
+    };
+    if (idx < FUL_BLK) {  // passes 1-3: the forward blocks with p21 in the fourth word, then the n31 words
+        const uint32_t m = idx < P2F - P1F ? 4 : idx < P3F - P1F ? 16 : 64, base = m == 4 ? 0 : m == 16 ? P2F - P1F : P3F - P1F;
+        uint32_t c = (idx - base) >> 2;
+        const uint32_t e = idx & 3;
+        // pass 3 in the order of the lanes that read it (lane bit k holds index bit lay(4).lane[k]), so that
+        // the 64 lanes' reads of blocks and n31 words are conflict-free both ways (tools/lds_tables4.py)
+        if (m == 64) c = (c & 7) | ((c & 8) << 1) | ((c & 16) << 1) | ((c & 32) >> 2);
+        out[T4_FUL + idx] = e == 3 ? pn(psi, m, c, false) : mont(psi[e == 0 ? m + c : 2 * m + 2 * c + (e - 1)]);
+        if (e == 3) out[T4_FUL + FUL_BLK + (idx >> 2)] = pn(psi, m, c, true);
+    }
+    if (idx < 4) out[T4_FU0 + idx] = pn(idx < 2 ? psi : ipsi, 1, 0, idx & 1);
+    if (idx < 4 * 256) out[T4_FU4 + idx] = pn((idx & 2) ? ipsi : psi, 256, idx >> 2, idx & 1);
 }
 
 #endif  // TFHE_FAST4_KERNEL_ONLY
@@ -766,8 +912,12 @@ hipError_t launch_blind_rotate_fast4_d6(const f4::FastConst& K, uint32_t n, uint
                                         const int32_t* bsk, const uint64_t* a, uint64_t* acc, size_t B, hipStream_t s);
 
 // blind_rotate_fast4_pair.hip: two ciphertexts per wavefront at three workgroups per CU, built under max-ilp
+// (fused: its radix-4 passes as fused groups, FU)
 hipError_t launch_blind_rotate_fast4_pair(const f4::FastConst& K, uint32_t n, uint32_t loga, const int32_t* tabs4,
-                                          const int32_t* bsk, const uint64_t* a, uint64_t* acc, size_t B, hipStream_t s);
+                                          const int32_t* bsk, const uint64_t* a, uint64_t* acc, size_t B, hipStream_t s,
+                                          bool fused);
+
+constexpr bool kPairFused = true;
 
 hipError_t launch_blind_rotate_fast4(int variant, const Fast4Shape& sh, const void* K, uint32_t n, uint32_t loga,
                                      const int32_t* tabs4, const int32_t* bsk, const uint64_t* a, uint64_t* acc,
@@ -805,15 +955,23 @@ hipError_t launch_blind_rotate_fast4(int variant, const Fast4Shape& sh, const vo
         dn->written = true;
         return hipGetLastError();
     }
-    // large batches, and variant 70 at every size: the pair instance (two ciphertexts per wavefront, each key
-    // row loaded feeds both).  A last, partly filled generation of its workgroups costs in proportion to its
+    // large batches, and variants 70 / 71 at every size: the pair instance (two ciphertexts per wavefront, each
+    // key row loaded feeds both).  A last, partly filled generation of its workgroups costs in proportion to its
     // size (7680 against 8192 ciphertexts, profiles/pair), so the batch is not split between the two kernels.
-    if (variant == 70 || (variant == 60 && pair_min > 0 && B >= (size_t)pair_min)) {
+    // 71 = the pair with fused radix-4 groups, 70 = with the plain butterflies; kPairFused is the one large
+    // batches of the default take (the adoption rule).
+    if (variant == 70 || variant == 71 || (variant == 60 && pair_min > 0 && B >= (size_t)pair_min)) {
         if (paired) *paired = true;
-        return launch_blind_rotate_fast4_pair(Kc, n, loga, tabs4, bsk, a, acc, B, s);
+        return launch_blind_rotate_fast4_pair(Kc, n, loga, tabs4, bsk, a, acc, B, s,
+                                              variant == 60 ? kPairFused : variant == 71);
     }
     switch (variant) {  // cross-check builds (blind_rotate_fast.hip known_variant)
         case 86: launch(f4::k_blind_rotate_fast4<4, 1, 0, 7, 1, 4>, 1, 1, 4); break;  // four per workgroup
+        // the default build with the inverse's passes L4 to L1 as fused groups: what fits its 128 VGPRs without
+        // scratch access in the round loop; kept for A/B runs against 60
+        case 61:
+            launch(f4::k_blind_rotate_fast4<4, 1, 0, 7, 1, 1, 4, 7, 0, true, false, false, 4, f4::FU_F0 | f4::FU_L | f4::FU_I1>, 1, 1);
+            break;
         default: launch(f4::k_blind_rotate_fast4<4, 1, 0, 7, 1>, 1, 1); break;  // = 60
     }
     return hipGetLastError();
@@ -826,19 +984,21 @@ hipError_t launch_blind_rotate_fast4(int variant, const Fast4Shape& sh, const vo
 // ---- arithmetic probes (test library only; arith_probes.hpp, tests/test_gpu_arith_units.py) ----
 // op: 0 sredc(T)  1 smul(a, w)  2 csub32(a, m)  3 bfly_ct(a, b, w)  4 / 5 bfly_gs<RED = 0 / 1>(a, b, w)
 //     6 fwd4(x[4], w1, w2, w3)  7 / 8 inv4<RED = 0 / 1>(x[4], w1, w2, w3)
+//     9 fwd4f(x[4], w1, w2, w3, p21, n31)  10 / 11 inv4f<RED = 0 / 1, MIR = 0>(x[4], w1, wa, wb, pa, pb)
+//     12 / 13 inv4f<RED = 0 / 1, MIR = 1>: the fused groups, 10 words in
 // 8 words in, 4 out per case (int32 values sign-extended to 64 bits, T as an int64); no table
 #include "arith_probes.hpp"
 
 namespace tfhe {
 namespace f4 {
-constexpr int F4P_NI = 8, F4P_NO = 4;
+constexpr int F4P_NI = 8, F4P_NO = 4, F4P_NIF = 10;
 __global__ void k_arith_fast4(int op, size_t cases, const uint64_t* __restrict__ in, const uint64_t* __restrict__,
                               size_t, uint64_t* __restrict__ out, FastConst K) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (!probe_lane_runs(op, i, cases)) return;
-    const int64_t* x = reinterpret_cast<const int64_t*>(in) + i * F4P_NI;
-    int64_t* o = reinterpret_cast<int64_t*>(out) + i * F4P_NO;
     const int f = op & 15;
+    const int64_t* x = reinterpret_cast<const int64_t*>(in) + i * (f >= 9 ? F4P_NIF : F4P_NI);
+    int64_t* o = reinterpret_cast<int64_t*>(out) + i * F4P_NO;
     if (f == 0) o[0] = sredc(x[0], K);
     else if (f == 1) o[0] = smul((int32_t)x[0], (int32_t)x[1], K);
     else if (f == 2) o[0] = (int64_t)(uint64_t)csub32((uint32_t)x[0], (uint32_t)x[1]);
@@ -856,16 +1016,26 @@ __global__ void k_arith_fast4(int op, size_t cases, const uint64_t* __restrict__
         else inv4<true>(v, w1, w2, w3, K);
 #pragma unroll
         for (int k = 0; k < 4; ++k) o[k] = v[k];
+    } else if (f >= 9 && f <= 13) {
+        int32_t v[4] = {(int32_t)x[0], (int32_t)x[1], (int32_t)x[2], (int32_t)x[3]};
+        const int32_t w1 = (int32_t)x[4], w2 = (int32_t)x[5], w3 = (int32_t)x[6], pa = (int32_t)x[7], pb = (int32_t)x[8];
+        if (f == 9) fwd4f(v, w1, w2, w3, pa, pb, K);
+        else if (f == 10) inv4f<false, false>(v, w1, w2, w3, pa, pb, K);
+        else if (f == 11) inv4f<true, false>(v, w1, w2, w3, pa, pb, K);
+        else if (f == 12) inv4f<false, true>(v, w1, w2, w3, pa, pb, K);
+        else inv4f<true, true>(v, w1, w2, w3, pa, pb, K);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = v[k];
     }
 }
 }  // namespace f4
 }  // namespace tfhe
 
 extern "C" TFHE_ARITH_PROBE(fast4) {
-    if ((op & 15) > 8 || Q < 3 || Q >= (1ull << 27) || !(Q & 1)) return -1;
+    if ((op & 15) > 13 || Q < 3 || Q >= (1ull << 27) || !(Q & 1)) return -1;
     tfhe::f4::FastConst K;
     tfhe::fast_const_build((uint32_t)Q, &K);
-    return tfhe::probe_launch(tfhe::f4::k_arith_fast4, tfhe::f4::F4P_NI, tfhe::f4::F4P_NO, op, cases, in, in_words, tab,
+    return tfhe::probe_launch(tfhe::f4::k_arith_fast4, (op & 15) >= 9 ? tfhe::f4::F4P_NIF : tfhe::f4::F4P_NI, tfhe::f4::F4P_NO, op, cases, in, in_words, tab,
                               tab_words, out, out_words, K);
 }
 #endif  // TFHE_TEST_PROBES
