@@ -60,6 +60,7 @@ def key_switch(p, ksk, ext, fmod):
 # sum: sum width in bits with packed sums / without; tiled False: the tiled form declines the shape.
 # ---------------------------------------------------------------------------------------------------------------
 ARB12 = ("STD128", True, 12, 0, 0, 1)
+LOGQ23 = ("STD128", False, 23, 0, 0, 1)
 
 CONTEXTS = {
     # PK form (packed u16 pairs mod 2^16), CTS 1 / 2 / 4
@@ -90,16 +91,29 @@ CONTEXTS = {
     # ks40_hbits = 0: the u64 words serve, though records could be packed
     "u64-2^38": dict(base=ARB12, qKS=1 << 38, kb=8, sums=(64, 64)),
     "u64-npot": dict(base=ARB12, qKS=(1 << 35) - 1, kb=8, sums=(64, 64)),
+    # the sweep of small LWE dimensions only (small_cases): logQ = 23, q = 2N beside ARB12's q = N
+    "split-b3-q2N": dict(base=LOGQ23, kb=5, kb0=8, sums=(64, 64), small_only=True),
 }
 
 FILLS = ("max", "even", "odd", "random")
 N_STAR = (32, 33, 47)  # a full last column tile, one column into a new tile, one short of full; n_pad > n at every width
 N_PLAIN = (33,)
+# Small LWE dimensions (tests/test_lwe_dimension_cpu.py, tests/test_gpu_lwe_dimension.py): one column, two, one short
+# of the 8 words of a u16 piece, exactly 8, one past.  n_pad (n rounded up to a 16-byte piece: 8 u16, 4 u32, 2 u64
+# words) is smaller than one column tile at every width, so every piece past it is a clamped one.
+N_SMALL = (1, 2, 7, 8, 9)
+SMALL = ("u16-packed", "u32-bound", "split-b3", "split-b3-q2N")  # each base set's own qKS and baseKS
 
 
 def cases():
     """(context name, n) of every edge context."""
-    return [(name, n) for name, c in CONTEXTS.items() for n in (N_STAR if c.get("star") else N_PLAIN)]
+    return [(name, n) for name, c in CONTEXTS.items() if not c.get("small_only")
+            for n in (N_STAR if c.get("star") else N_PLAIN)]
+
+
+def small_cases(names=SMALL):
+    """(context name, n) of the small-n sweep."""
+    return [(name, n) for name in names for n in N_SMALL]
 
 
 def dks_for(qKS, baseKS):

@@ -46,10 +46,10 @@ def window(d_max):
     return 1 << (w - 1).bit_length()
 
 
-def sweep_context(oracle, base, gpu=True, seed=SEED):
-    """(orc, ctx, s): the oracle context, the GPU context (None without `gpu`) and the centred secret (int64,
-    ternary) of `base` with n lowered to 32: tfhe_params_finish through the C-ABI, the fields mirrored into the
-    oracle's Params (as tests/test_gpu_modulus_edges.py::_edge_pair), and *valid* keys: or_keygen(seed), a real KSK."""
+def lowered_params(oracle, base, n=N32, Q=None, baseG_log=None):
+    """(cp, op): the engine's and the oracle's parameters of `base` (a set name or a params_from_logq argument
+    tuple) at LWE dimension n, with Q / baseG overwritten where given: tfhe_params_finish through the C-ABI, the
+    fields it derives mirrored into the oracle's Params."""
     import tfhe_amd
     from tfhe_amd import capi as raw
 
@@ -57,17 +57,32 @@ def sweep_context(oracle, base, gpu=True, seed=SEED):
         cp, op = tfhe_amd.params_from_set(base), oracle.params_from_set(base)
     else:
         cp, op = tfhe_amd.params_from_logq(*base), oracle.params_from_logq(*base)
-    cp.n = N32
+    cp.n = n
+    if Q is not None:
+        cp.Q = Q
+    if baseG_log is not None:
+        cp.baseG = 1 << baseG_log
     cp.digitsG = cp.dG2 = 0
     raw.check(raw.lib().tfhe_params_finish(C.byref(cp)), "tfhe_params_finish")
     for k in ("n", "Q", "baseG", "digitsG", "dG2", "numDigitsToThrow"):
         setattr(op, k, getattr(cp, k))
     op.logG = cp.baseG.bit_length() - 1
     assert (op.N, op.q, op.qKS, op.baseKS, op.dKS) == (cp.N, cp.q, cp.qKS, cp.baseKS, cp.dKS)
+    return cp, op
+
+
+def sweep_context(oracle, base, gpu=True, seed=SEED, n=N32):
+    """(orc, ctx, s): the oracle context, the GPU context (None without `gpu`) and the centred secret (int64,
+    ternary) of `base` with n lowered (32 unless given): lowered_params, and *valid* keys: or_keygen(seed), a real
+    KSK."""
+    import tfhe_amd
+
+    cp, op = lowered_params(oracle, base, n)
     sk, bsk, ksk = oracle.keygen(op, oracle.Rng(seed))
     # or_keygen writes s as ternary words mod qKS
     s = np.where(sk > np.uint64(op.qKS // 2), sk.astype(np.int64) - np.int64(op.qKS), sk.astype(np.int64))
-    assert set(np.unique(s)) <= {-1, 0, 1} and np.any(s == 1) and np.any(s == -1)
+    assert set(np.unique(s)) <= {-1, 0, 1}
+    assert n < N32 or (np.any(s == 1) and np.any(s == -1))  # (a key of a few words may miss a value)
     orc = oracle.Oracle(op, bsk, ksk)
     ctx = tfhe_amd.BinFHEContextHIP(cp).GPUSetup(bsk, ksk) if gpu else None
     return orc, ctx, s

@@ -68,6 +68,20 @@ def test_errors_without_setup(capi):
     assert lib.tfhe_host_selftest(ctypes.byref(bad)) == 1
 
 
+def test_params_finish_rejects_zero_lwe_dimension(capi):
+    """n = 0 (no blind-rotation round, no key-switch column, empty keys) is an invalid argument with a message,
+    for tfhe_params_finish and for whatever finishes the caller's parameters itself; n = 1 is the smallest."""
+    lib = capi.lib()
+    p = capi.params_from_set("STD128")
+    p.n = 0
+    assert lib.tfhe_params_finish(ctypes.byref(p)) == 1  # TFHE_ERR_INVALID_ARGUMENT
+    assert b"LWE dimension" in lib.tfhe_last_error()
+    assert lib.tfhe_host_selftest(ctypes.byref(p)) == 1
+    p.n = 1
+    assert lib.tfhe_params_finish(ctypes.byref(p)) == 0
+    assert (p.n, p.digitsG, p.dG2, p.dKS) == (1, 4, 8, 2)
+
+
 def test_key_file_rejected_before_device_use(tmp_path):
     """tfhe_setup_from_key_file validates the header (magic, ABI, parameters, size,
     checksum) before any device call, so these checks run without a GPU."""

@@ -20,8 +20,6 @@ Moduli (all prime, = 1 mod 2N; digit counts as tfhe_params_finish derives them):
   sf      Q = 2^54 - 876543 (the largest c of the 20 NTT-friendly primes in range), logQ = 12 arbFunc
           throw = 1 (baseG 2^27, one digit) and logQ = 23 throw = 1 (baseG 2^18, two digits)
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -30,31 +28,25 @@ pytestmark = pytest.mark.gpu
 N32 = 32  # the lowered LWE dimension
 
 
-def _edge_pair(oracle, base, Q, baseG_log=None, expect_digits=None):
+def _edge_pair(oracle, base, Q=None, baseG_log=None, expect_digits=None, n=N32, keys=None):
     """(cp, op, ctx, orc) for `base` (a set name or a params_from_logq argument tuple) with Q / baseG
-    overridden and n = 32; first BSK rows at the key edges, zero KSK."""
+    overridden (Q = None: the base's own) and the LWE dimension lowered to n; first BSK rows at the key edges,
+    zero KSK.  keys: a function (cp, op) -> (bsk, ksk) that supplies the keys instead
+    (tests/test_gpu_lwe_dimension.py: a random KSK, slices of another context's BSK)."""
     import tfhe_amd
-    from tfhe_amd import capi as raw
+    from phases import lowered_params
 
-    if isinstance(base, str):
-        cp, op = tfhe_amd.params_from_set(base), oracle.params_from_set(base)
-    else:
-        cp, op = tfhe_amd.params_from_logq(*base), oracle.params_from_logq(*base)
-    cp.Q = Q
-    cp.n = N32
-    if baseG_log is not None:
-        cp.baseG = 1 << baseG_log
-    cp.digitsG = cp.dG2 = 0
-    raw.check(raw.lib().tfhe_params_finish(C.byref(cp)), "tfhe_params_finish")
-    for k in ("n", "Q", "baseG", "digitsG", "dG2", "numDigitsToThrow"):
-        setattr(op, k, getattr(cp, k))
-    op.logG = cp.baseG.bit_length() - 1
+    cp, op = lowered_params(oracle, base, n, Q, baseG_log)
+    Q = int(cp.Q)
     if expect_digits is not None:
         assert cp.digitsG - cp.numDigitsToThrow == expect_digits, cp.as_dict()
-    rs = np.random.default_rng(Q % (1 << 32))
-    bsk = rs.integers(0, Q, cp.bsk_words(), dtype=np.uint64)
-    bsk[: 4 * cp.N] = np.array([0, Q - 1, Q >> 1, (Q >> 1) + 1], dtype=np.uint64).repeat(cp.N)
-    ksk = np.zeros(cp.ksk_words(), dtype=np.uint64)
+    if keys is not None:
+        bsk, ksk = keys(cp, op)
+    else:
+        rs = np.random.default_rng(Q % (1 << 32))
+        bsk = rs.integers(0, Q, cp.bsk_words(), dtype=np.uint64)
+        bsk[: 4 * cp.N] = np.array([0, Q - 1, Q >> 1, (Q >> 1) + 1], dtype=np.uint64).repeat(cp.N)
+        ksk = np.zeros(cp.ksk_words(), dtype=np.uint64)
     ctx = tfhe_amd.BinFHEContextHIP(cp).GPUSetup(bsk, ksk)
     orc = oracle.Oracle(op, bsk, ksk)
     return cp, op, ctx, orc

@@ -229,6 +229,7 @@ tfhe_status params_finish(tfhe_params* p, std::string* err) {
         if (err) *err = m;
         return TFHE_ERR_INVALID_ARGUMENT;
     };
+    if (p->n == 0) return fail("LWE dimension n must be at least 1");
     if (p->N < 16 || (p->N & (p->N - 1))) return fail("N must be a power of two >= 16");
     if (p->baseG < 2 || (p->baseG & (p->baseG - 1))) return fail("gadget base must be a power of two");
     if (p->Q < 3 || p->Q % (2ull * p->N) != 1) return fail("Q must be a prime = 1 mod 2N");
