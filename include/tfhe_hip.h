@@ -502,6 +502,53 @@ tfhe_status tfhe_eval_pool2d_tables_device(tfhe_ctx* ctx, const tfhe_pool2d* d, 
 tfhe_status tfhe_eval_pool2d_tables(tfhe_ctx* ctx, const tfhe_pool2d* d, size_t instances, const uint64_t* ct,
                                     uint64_t q, const uint64_t* luts, size_t num_luts, uint64_t* out);
 
+/* ---- products of two encrypted tensors: elementwise and matrix (no reference counterpart; new symbols only, the
+ * ABI version stays) ----
+ * The pair form: with luts[2][q] (luts[0] for the sums, luts[1] for the differences), q a power of two, every step on
+ * all n+1 words,
+ *   out[i][r][c] = sum_{k < inner} ( EvalFunc(x[i][r][k] + y[i][k][c] mod q, luts[0])
+ *                                  - EvalFunc(x[i][r][k] - y[i][k][c] mod q, luts[1]) )  mod q,
+ * EvalFunc being tfhe_eval_func with that table shared.  With the quarter-square tables (tfhe_amd.product_tables:
+ * both rows the staircase of floor(s^2 / 4)) it is the matrix product of the messages, since x y = floor((x + y)^2 /
+ * 4) - floor((x - y)^2 / 4) exactly for integers; other tables give other functions of the sum and the difference.
+ * Layouts: x[instances][rows][inner][n+1]; y[instances][inner][cols][n+1], with y_transposed
+ * y[instances][cols][inner][n+1] (Q K^T), with y_shared the instances axis is absent and every instance reads the
+ * same y (encrypted weights); out[instances][rows][cols][n+1].  Elementwise multiplication is rows = inner = cols = 1
+ * with instances = the number of elements.  The result equals the formula composed on host arrays with tfhe_eval_func
+ * and wrap-around adds, bit for bit.  Each table is classified on its own by the reference's checkInputFunction, as
+ * tfhe_eval_func_tables does, and the two classes may differ; an arbitrary-class table with q > N is
+ * TFHE_ERR_UNSUPPORTED before anything is launched and the counter does not move.  tfhe_info.bootstraps grows by
+ * P (b0 + b1), P = instances rows inner cols, b = 1 for a negacyclic table and 2 otherwise.
+ * Slicing: the 2 P look-ups are one flat EvalFunc batch (sums, then differences) in slices of whole outputs, so no
+ * output is reduced across slices: a slice is floor(min(scratch capacity, 65,536) / (2 inner)) outputs; 2 inner above
+ * 65,536 is TFHE_ERR_UNSUPPORTED before any launch.  No input word is written; d_out must not overlap an input.
+ * Argument errors -- a null pointer, instances or a dimension = 0, a flag other than 0 or 1, q < 8, q not a power of
+ * two or not dividing 2N, a size product that overflows size_t, a table entry >= q in eval_plain -- are
+ * TFHE_ERR_INVALID_ARGUMENT with a message naming the field, reported before any device call; a buffer on a device
+ * the context does not use is TFHE_ERR_INVALID_ARGUMENT as for the other _device calls. */
+typedef struct tfhe_ct_matmul {
+    uint32_t rows, inner, cols;  /* >= 1 */
+    uint32_t y_transposed;       /* 0: y[..][inner][cols]; 1: y[..][cols][inner] */
+    uint32_t y_shared;           /* 0: one y per instance; 1: one y for all */
+} tfhe_ct_matmul;
+
+/* host only, no GPU (q need only be a power of two >= 8): *products = P, *bootstraps = what the call adds to
+ * tfhe_info.bootstraps (either pointer may be NULL) */
+tfhe_status tfhe_ct_matmul_info(const tfhe_ct_matmul* d, size_t instances, uint64_t q, const uint64_t* luts,
+                                size_t* products, uint64_t* bootstraps);
+/* host only, no GPU: the same formula on clear values mod q, EvalFunc(v, t) = t[v]: x[instances][rows][inner],
+ * y and out likewise without the n+1 axis */
+tfhe_status tfhe_ct_matmul_eval_plain(const tfhe_ct_matmul* d, size_t instances, uint64_t q, const uint64_t* luts,
+                                      const uint64_t* x, const uint64_t* y, uint64_t* out);
+/* device = the one holding d_out; ordered on `stream`.  Uses the dense layer's grow-only store (four rows per
+ * look-up pair of a slice); reads the 2 q table words back once per call */
+tfhe_status tfhe_eval_ct_matmul_device(tfhe_ctx* ctx, const tfhe_ct_matmul* d, size_t instances, const uint64_t* d_x,
+                                       const uint64_t* d_y, uint64_t q, const uint64_t* d_luts, uint64_t* d_out,
+                                       void* stream);
+/* the same on host arrays, staged through the context's first device as tfhe_eval_pool2d */
+tfhe_status tfhe_eval_ct_matmul(tfhe_ctx* ctx, const tfhe_ct_matmul* d, size_t instances, const uint64_t* x,
+                                const uint64_t* y, uint64_t q, const uint64_t* luts, uint64_t* out);
+
 /* ---- key generation, encryption and decryption on the device (no reference counterpart; new symbols only, the
  * ABI version stays) ----
  * FOR TESTS, BENCHMARKS AND REPRODUCIBLE EXPERIMENTS.  The generator is splitmix64 from a 64-bit seed: it

@@ -997,6 +997,31 @@ tfhe_status dev_pool2d(tfhe_ctx* c, Device& d, int prop, const Device::PoolPlanD
     return TFHE_OK;
 }
 
+// ---------------------------------------------------------------------------
+// the product of two encrypted tensors on one device (inside run_device_op)
+// ---------------------------------------------------------------------------
+// out[o] = sum_k EvalFunc(x + y, table 0) - EvalFunc(x - y, table 1) over the products (o, k) of output
+// o = (i rows + r) cols + c.  Slices of `slice` whole outputs, so no output is reduced across slices: the sums and
+// the differences into the first half of d.dense_z, one EvalFunc batch of 2 count ciphertexts under tc's two tables
+// (inner = count: the first half takes table 0, the second table 1) into the second half, the signed sum over k
+// into out.  2 inner slice <= the scratch capacity and the chunk limit (ct_matmul_on_device).
+tfhe_status dev_ct_matmul(tfhe_ctx* c, Device& d, const tfhe_ct_matmul& m, size_t instances, size_t slice,
+                          const uint64_t* x, const uint64_t* y, uint64_t q, uint64_t* out, const TabCall& tc) {
+    const size_t w = c->p.n + 1, total = instances * m.rows * m.cols;
+    CtmmArgs a{};
+    a.x = x, a.y = y, a.rows = m.rows, a.inner = m.inner, a.cols = m.cols;
+    a.y_transposed = m.y_transposed, a.y_shared = m.y_shared;
+    a.width = (uint32_t)w, a.mask = q - 1;
+    for (a.first_out = 0; a.first_out < total; a.first_out += slice) {
+        a.count = std::min(slice, total - a.first_out) * m.inner;
+        uint64_t *z = d.dense_z, *f = d.dense_z + 2 * a.count * w;
+        HCHECK(launch_ctmm_pairs(a, z, d.stream));
+        SCHECK(dev_func_tables(c, d, tc, a.count, 0, z, q, f, 2 * a.count));
+        HCHECK(launch_ctmm_reduce(a, f, out, d.stream));
+    }
+    return TFHE_OK;
+}
+
 void circuit_plan_free(int device, void* base) {
     int cur = 0;
     const bool have = hipGetDevice(&cur) == hipSuccess;
@@ -3590,6 +3615,162 @@ tfhe_status tfhe_eval_pool2d_tables(tfhe_ctx* c, const tfhe_pool2d* desc, size_t
         SCHECK(check_pool_args("EvalPool2d", desc, instances, ct, q, c->p.N, luts, out, c->p.n + 1, g, pairs));
         SCHECK(check_layer_tables(c, "EvalPool2d", q, num_luts, g.c, "c"));
         return pool_from_host(c, g, instances, ct, q, luts, out, num_luts);
+    });
+}
+
+extern "C++" {
+namespace {
+// The sizes of a product call: P = instances rows inner cols, and the rows of x, y and out.
+struct CtmmSizes {
+    size_t products, x_rows, y_rows, out_rows;
+};
+
+// what the product calls check before any device call (N = 0: no context, q need only be a power of two >= 8);
+// `words` is n+1, or 1 for clear values; every message names the field
+tfhe_status check_ct_matmul_args(const char* who, const tfhe_ct_matmul* m, size_t instances, uint64_t q, uint64_t N,
+                                 size_t words, CtmmSizes& sz) {
+    const auto bad = [who](const std::string& what) {
+        return fail(TFHE_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what);
+    };
+    if (!m) return bad("null descriptor");
+    if (instances == 0) return bad("instances is 0");
+    if (m->rows == 0) return bad("rows is 0");
+    if (m->inner == 0) return bad("inner is 0");
+    if (m->cols == 0) return bad("cols is 0");
+    if (m->y_transposed > 1) return bad("y_transposed must be 0 or 1");
+    if (m->y_shared > 1) return bad("y_shared must be 0 or 1");
+    if (q < 8 || (q & (q - 1)) != 0 || (N && (2ull * N) % q != 0))
+        return bad(N ? "q must be a power of two >= 8 that divides 2N" : "q must be a power of two >= 8");
+    // the inputs and the output in bytes, and what a slice can need at most: four flat rows per product
+    size_t xs = 1, ys = 1, os = 1, mid = 4 * sizeof(uint64_t);
+    const bool ok = conv_mul(xs, instances) && conv_mul(xs, m->rows) && conv_mul(xs, m->inner) &&
+                    conv_mul(ys, m->y_shared ? 1 : instances) && conv_mul(ys, m->inner) && conv_mul(ys, m->cols) &&
+                    conv_mul(os, instances) && conv_mul(os, m->rows) && conv_mul(os, m->cols) &&
+                    conv_mul(mid, instances) && conv_mul(mid, m->rows) && conv_mul(mid, m->inner) &&
+                    conv_mul(mid, m->cols) && conv_mul(mid, words);
+    size_t xb = xs, yb = ys, ob = os, all = 0;
+    if (!ok || q > SIZE_MAX / (4 * sizeof(uint64_t)) || !conv_mul(xb, words * sizeof(uint64_t)) || !conv_mul(yb, words * sizeof(uint64_t)) ||
+        !conv_mul(ob, words * sizeof(uint64_t)) || xb > SIZE_MAX - yb || (all = xb + yb) > SIZE_MAX - ob ||
+        (all += ob) > SIZE_MAX - 2 * q * sizeof(uint64_t))
+        return bad("sizes overflow");
+    sz = CtmmSizes{os * m->inner, xs, ys, os};
+    return TFHE_OK;
+}
+
+tfhe_status check_ct_matmul_call(tfhe_ctx* c, const tfhe_ct_matmul* m, size_t instances, const void* x, const void* y,
+                                 uint64_t q, const void* luts, const void* out, CtmmSizes& sz) {
+    SCHECK(check_ctx(c));
+    if (!x) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalCtMatMul: null x");
+    if (!y) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalCtMatMul: null y");
+    if (!luts) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalCtMatMul: null luts");
+    if (!out) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalCtMatMul: null out");
+    SCHECK(check_ct_matmul_args("EvalCtMatMul", m, instances, q, c->p.N, c->p.n + 1, sz));
+    if (2 * (size_t)m->inner > c->max_chunk)
+        return fail(TFHE_ERR_UNSUPPORTED, "EvalCtMatMul: 2 inner exceeds the chunk limit of " +
+                                              std::to_string(c->max_chunk) + " ciphertexts: an output's products are one EvalFunc batch");
+    return TFHE_OK;
+}
+
+// d_out selects the device; the two tables are read back once and classified one by one (pre: the host-array
+// form's classes of its host copy)
+tfhe_status ct_matmul_on_device(tfhe_ctx* c, const tfhe_ct_matmul& m, size_t instances, const CtmmSizes& sz,
+                                const uint64_t* d_x, const uint64_t* d_y, uint64_t q, const uint64_t* d_luts,
+                                uint64_t* d_out, void* stream, const TabCall* pre = nullptr) {
+    Device* dp = nullptr;
+    SCHECK(device_for(c, d_out, dp));
+    HCHECK(hipSetDevice(dp->id));
+    TabCall tc;
+    SCHECK(tab_prepare(c, *dp, stream, q, d_luts, 2, tc, pre));
+    // whole outputs per slice: 2 inner look-ups each, as many as the chunk limit admits (the frame grows the
+    // scratch to B, so the scratch capacity never binds first)
+    const size_t slice = std::min(sz.out_rows, c->max_chunk / (2 * (size_t)m.inner)), B = 2 * slice * m.inner;
+    SCHECK(ensure_words(*dp, dp->dense_z, dp->dense_z_words, 2 * B * (c->p.n + 1)));
+    return run_device_op(c, B, d_out, stream, [&](Device& d) {
+        SCHECK(tab_upload(d, tc));
+        return dev_ct_matmul(c, d, m, instances, slice, d_x, d_y, q, d_out, tc);
+    });
+}
+}  // namespace
+}  // extern "C++"
+
+tfhe_status tfhe_ct_matmul_info(const tfhe_ct_matmul* m, size_t instances, uint64_t q, const uint64_t* luts,
+                                size_t* products, uint64_t* bootstraps) {
+    return guarded([&]() -> tfhe_status {
+        if (!luts) return fail(TFHE_ERR_INVALID_ARGUMENT, "CtMatMulInfo: null luts");
+        CtmmSizes sz;
+        SCHECK(check_ct_matmul_args("CtMatMulInfo", m, instances, q, 0, 1, sz));
+        uint64_t per = 0;
+        for (int t = 0; t < 2; ++t) per += check_input_function(luts + t * q, q, q) == 0 ? 1 : 2;
+        if (sz.products > UINT64_MAX / per) return fail(TFHE_ERR_INVALID_ARGUMENT, "CtMatMulInfo: sizes overflow");
+        if (products) *products = sz.products;
+        if (bootstraps) *bootstraps = sz.products * per;
+        return TFHE_OK;
+    });
+}
+
+tfhe_status tfhe_ct_matmul_eval_plain(const tfhe_ct_matmul* m, size_t instances, uint64_t q, const uint64_t* luts,
+                                      const uint64_t* x, const uint64_t* y, uint64_t* out) {
+    return guarded([&]() -> tfhe_status {
+        if (!luts) return fail(TFHE_ERR_INVALID_ARGUMENT, "CtMatMulEvalPlain: null luts");
+        if (!x) return fail(TFHE_ERR_INVALID_ARGUMENT, "CtMatMulEvalPlain: null x");
+        if (!y) return fail(TFHE_ERR_INVALID_ARGUMENT, "CtMatMulEvalPlain: null y");
+        if (!out) return fail(TFHE_ERR_INVALID_ARGUMENT, "CtMatMulEvalPlain: null out");
+        CtmmSizes sz;
+        SCHECK(check_ct_matmul_args("CtMatMulEvalPlain", m, instances, q, 0, 1, sz));
+        for (uint64_t t = 0; t < 2 * q; ++t)
+            if (luts[t] >= q)
+                return fail(TFHE_ERR_INVALID_ARGUMENT, "CtMatMulEvalPlain: luts[" + std::to_string(t / q) + "][" +
+                                                           std::to_string(t % q) + "] is not below q");
+        const uint64_t mask = q - 1;
+        const size_t R = m->rows, K = m->inner, Cn = m->cols;
+        for (size_t i = 0; i < instances; ++i) {
+            const uint64_t* yi = y + (m->y_shared ? 0 : i * K * Cn);
+            for (size_t r = 0; r < R; ++r)
+                for (size_t cc = 0; cc < Cn; ++cc) {
+                    uint64_t acc = 0;
+                    for (size_t k = 0; k < K; ++k) {
+                        const uint64_t a = x[(i * R + r) * K + k], b = yi[m->y_transposed ? cc * K + k : k * Cn + cc];
+                        acc += luts[(a + b) & mask] - luts[q + ((a - b) & mask)];
+                    }
+                    out[(i * R + r) * Cn + cc] = acc & mask;
+                }
+        }
+        return TFHE_OK;
+    });
+}
+
+tfhe_status tfhe_eval_ct_matmul_device(tfhe_ctx* c, const tfhe_ct_matmul* m, size_t instances, const uint64_t* d_x,
+                                       const uint64_t* d_y, uint64_t q, const uint64_t* d_luts, uint64_t* d_out,
+                                       void* stream) {
+    return guarded([&]() -> tfhe_status {
+        CtmmSizes sz;
+        SCHECK(check_ct_matmul_call(c, m, instances, d_x, d_y, q, d_luts, d_out, sz));
+        return ct_matmul_on_device(c, *m, instances, sz, d_x, d_y, q, d_luts, d_out, stream);
+    });
+}
+
+tfhe_status tfhe_eval_ct_matmul(tfhe_ctx* c, const tfhe_ct_matmul* m, size_t instances, const uint64_t* x,
+                                const uint64_t* y, uint64_t q, const uint64_t* luts, uint64_t* out) {
+    return guarded([&]() -> tfhe_status {
+        CtmmSizes sz;
+        SCHECK(check_ct_matmul_call(c, m, instances, x, y, q, luts, out, sz));
+        TabCall pre;
+        SCHECK(check_host_tables(c, luts, 2, q, pre));
+        Device& d = c->devs[0];
+        HCHECK(hipSetDevice(d.id));
+        const size_t w = c->p.n + 1, wx = sz.x_rows * w, wy = sz.y_rows * w, wl = 2 * q, wo = sz.out_rows * w;
+        // one block: x | y | luts | out
+        DevBuf buf;
+        HCHECK(hipMalloc(&buf.p, (wx + wy + wl + wo) * sizeof(uint64_t)));
+        uint64_t *dx = buf.as<uint64_t>(), *dy = dx + wx, *dl = dy + wy, *dout = dl + wl;
+        tfhe_status st = h2d_staged(d, dx, flat_rows(x, w), wx, d.stream);
+        if (st == TFHE_OK) st = h2d_staged(d, dy, flat_rows(y, w), wy, d.stream);
+        if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(luts, q), wl, d.stream);
+        if (st == TFHE_OK) st = ct_matmul_on_device(c, *m, instances, sz, dx, dy, q, dl, dout, nullptr, &pre);
+        if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
+        const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
+        if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalCtMatMul: ") + hipGetErrorString(e));
+        return st;
     });
 }
 

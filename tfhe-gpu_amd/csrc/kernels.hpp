@@ -358,4 +358,23 @@ hipError_t launch_pool_diff(const PoolArgs& p, uint64_t* z, hipStream_t s);
 hipError_t launch_pool_add(const PoolArgs& p, const uint64_t* f, hipStream_t s);
 hipError_t launch_pool_copy(const PoolArgs& p, hipStream_t s);
 
+// The streaming kernels around the EvalFunc batch of a product of two encrypted tensors (ct_matmul.hip; DESIGN
+// 3.13).  A slice holds the whole outputs [first_out, first_out + count / inner), o = (i rows + r) cols + c; item
+// `it` < count is product (o, k) = (first_out + it / inner, it mod inner).  launch_ctmm_pairs writes z[it] = x + y
+// and z[count + it] = x - y mod q for x = x[i][r][k], y = y[i][k][c] ([c][k] with y_transposed, no i with y_shared);
+// launch_ctmm_reduce writes out[o] = sum_k f[o' inner + k] - f[count + o' inner + k] mod q.  x and y are only read;
+// mask = q - 1; z and f hold 2 count rows.  A workgroup of CM_THREADS threads takes CM_ITEMS items at a time, one per
+// wave.
+constexpr int CM_THREADS = 256, CM_ITEMS = CM_THREADS / 64;
+struct CtmmArgs {
+    const uint64_t* x;
+    const uint64_t* y;
+    uint32_t rows, inner, cols, y_transposed, y_shared;
+    uint32_t width;
+    uint64_t mask;
+    size_t first_out, count;
+};
+hipError_t launch_ctmm_pairs(const CtmmArgs& p, uint64_t* z, hipStream_t s);
+hipError_t launch_ctmm_reduce(const CtmmArgs& p, const uint64_t* f, uint64_t* out, hipStream_t s);
+
 }  // namespace tfhe

@@ -14,10 +14,11 @@ library or a GPU is missing, calls raise.
 """
 from .capi import (BINGATE, CIRCUIT_OPS, FCIRCUIT_OPS, PARAMSETS, TfheError, Params, lib, library_path, build, exported_symbols,
                    params_from_set, params_from_logq, host_selftest, mm_tiles, Conv2d, conv2d_shape, conv2d_tiles, Pool2d, pool2d_shape,
-                   pool2d_eval_plain, max_table, lut_classes, lut_tables_info)
+                   pool2d_eval_plain, max_table, lut_classes, lut_tables_info, CtMatMul, ct_matmul_info, ct_matmul_eval_plain,
+                   product_tables)
 from .circuit import Circuit
 from .fcircuit import FuncCircuit
 from .context import BinFHEContextHIP, keygen
 
 __all__ = ["BINGATE", "CIRCUIT_OPS", "Circuit", "FCIRCUIT_OPS", "FuncCircuit", "PARAMSETS", "TfheError", "Params", "lib", "library_path", "build", "exported_symbols",
-           "params_from_set", "params_from_logq", "host_selftest", "mm_tiles", "Conv2d", "conv2d_shape", "conv2d_tiles", "Pool2d", "pool2d_shape", "pool2d_eval_plain", "max_table", "lut_classes", "lut_tables_info", "BinFHEContextHIP", "keygen"]
+           "params_from_set", "params_from_logq", "host_selftest", "mm_tiles", "Conv2d", "conv2d_shape", "conv2d_tiles", "Pool2d", "pool2d_shape", "pool2d_eval_plain", "max_table", "lut_classes", "lut_tables_info", "CtMatMul", "ct_matmul_info", "ct_matmul_eval_plain", "product_tables", "BinFHEContextHIP", "keygen"]

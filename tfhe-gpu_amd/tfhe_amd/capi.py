@@ -106,6 +106,22 @@ class Pool2d(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CtMatMul(C.Structure):
+    """tfhe_ct_matmul: the shape of a product of two encrypted tensors (include/tfhe_hip.h)."""
+    _fields_ = [(k, C.c_uint32) for k in ("rows", "inner", "cols", "y_transposed", "y_shared")]
+
+    def __init__(self, rows=0, inner=0, cols=0, y_transposed=0, y_shared=0):
+        super().__init__(rows, inner, cols, int(y_transposed), int(y_shared))
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+    def y_shape(self, instances: int) -> tuple:
+        """The shape of y without the n+1 axis."""
+        kc = (self.cols, self.inner) if self.y_transposed else (self.inner, self.cols)
+        return kc if self.y_shared else (instances,) + kc
+
+
 u64p = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")
 i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
 VP = C.c_void_p
@@ -183,6 +199,10 @@ _SIGS = {
     "tfhe_eval_conv2d_tables": ([VP, VP, SZ, u64p, i64p, VP, U64, u64p, SZ, u64p], C.c_int),
     "tfhe_eval_pool2d_tables_device": ([VP, VP, SZ, VP, U64, VP, SZ, VP, VP], C.c_int),
     "tfhe_eval_pool2d_tables": ([VP, VP, SZ, u64p, U64, u64p, SZ, u64p], C.c_int),
+    "tfhe_ct_matmul_info": ([VP, SZ, U64, VP, C.POINTER(SZ), C.POINTER(U64)], C.c_int),
+    "tfhe_ct_matmul_eval_plain": ([VP, SZ, U64, VP, VP, VP, VP], C.c_int),
+    "tfhe_eval_ct_matmul_device": ([VP, VP, SZ, VP, VP, U64, VP, VP, VP], C.c_int),
+    "tfhe_eval_ct_matmul": ([VP, VP, SZ, u64p, u64p, U64, u64p, u64p], C.c_int),
     "tfhe_keygen_device": ([P, U64, C.c_int, VP, VP, VP, C.POINTER(U64), VP], C.c_int),
     "tfhe_setup_keygen": ([C.POINTER(VP), P, U64, C.c_int, u64p, C.POINTER(U64)], C.c_int),
     "tfhe_encrypt_device": ([P, C.c_int, VP, SZ, VP, U64, U64, U64, VP, C.POINTER(U64), VP], C.c_int),
@@ -372,6 +392,82 @@ def max_table(q: int, negacyclic: bool = False):
     half = np.where(x[:q // 2] < q // 4, x[:q // 2], 0)
     half[half == 0] = 1
     return np.concatenate([half, q - half]).astype(np.uint64)
+
+
+def _pair_tables(who: str, luts, q: int):
+    t = np.ascontiguousarray(luts, dtype=np.uint64)
+    if t.shape != (2, q):
+        raise ValueError(f"{who}: tables must have shape (2, {q}), got {t.shape}")
+    return t
+
+
+def ct_matmul_info(desc: CtMatMul, instances: int, luts, q: int) -> tuple[int, int]:
+    """(products P = instances rows inner cols, bootstraps the call adds: P (b0 + b1), b = 1 for a negacyclic table
+    and 2 otherwise) of a product of two encrypted tensors under luts[2, q] (tfhe_ct_matmul_info; no GPU)."""
+    t = _pair_tables("ct_matmul_info", luts, q)
+    products, boots = SZ(), U64()
+    check(lib().tfhe_ct_matmul_info(C.byref(desc), instances, q, C.c_void_p(t.ctypes.data), C.byref(products),
+                                    C.byref(boots)), "tfhe_ct_matmul_info")
+    return products.value, boots.value
+
+
+def ct_matmul_eval_plain(desc: CtMatMul, x, y, luts, q: int):
+    """The pair form on clear values mod q: x[instances, rows, inner], y[instances, inner, cols] ([inner, cols] when
+    desc.y_shared; the last two axes swapped when desc.y_transposed) and luts[2, q] -> [instances, rows, cols],
+    out = sum_k luts[0][x + y mod q] - luts[1][x - y mod q] mod q (tfhe_ct_matmul_eval_plain; no GPU)."""
+    x = np.ascontiguousarray(x, dtype=np.uint64)
+    y = np.ascontiguousarray(y, dtype=np.uint64)
+    if x.ndim != 3 or x.shape[1:] != (desc.rows, desc.inner):
+        raise ValueError(f"ct_matmul_eval_plain: x: expected shape (instances, {desc.rows}, {desc.inner}), got {x.shape}")
+    if y.shape != desc.y_shape(x.shape[0]):
+        raise ValueError(f"ct_matmul_eval_plain: y: expected shape {desc.y_shape(x.shape[0])}, got {y.shape}")
+    t = _pair_tables("ct_matmul_eval_plain", luts, q)
+    out = np.empty((x.shape[0], desc.rows, desc.cols), dtype=np.uint64)
+    check(lib().tfhe_ct_matmul_eval_plain(C.byref(desc), x.shape[0], q, C.c_void_p(t.ctypes.data),
+                                          C.c_void_p(x.ctypes.data), C.c_void_p(y.ctypes.data),
+                                          C.c_void_p(out.ctypes.data)), "tfhe_ct_matmul_eval_plain")
+    return out
+
+
+def product_tables(q: int, p: int, negacyclic: bool = False):
+    """The two tables [2, q] (both rows equal) that make EvalCtMatMul / EvalCtMul a product of messages mod p, by the
+    quarter-square identity x y = floor((x + y)^2 / 4) - floor((x - y)^2 / 4): with Delta = q / p and s the signed
+    message of a step, the staircase Delta (floor(s^2 / 4) mod p).
+
+    Default (arbitrary class, needs q <= N, 4 bootstraps per product): s in [-p/2, p/2).  Exact for messages with
+    |x| + |y| <= p/2 -- the wrap at +-p/2 has the same square -- so messages in [0, p/4] or signed ones in
+    [-p/4, p/4].
+
+    negacyclic=True (2 bootstraps per product), for |x| + |y| < p/4, one more bit of headroom: on [0, q/4) the
+    squares of s = 0 ... p/4 - 1, on [q/4, q/2) q minus the squares of s = h - p/2, and the upper half mirrored,
+    lut[v + q/2] = q - lut[v], which gives negative s their positive square.  checkInputFunction compares lut[i]
+    with q - lut[i + q/2], so a zero entry can never pass as negacyclic: the helper writes 1 for those zeros and
+    q - 1 for their mirrors, as max_table does.  A product is then off by at most 2 units of the noise bits.
+
+    On ciphertexts EvalFunc looks a table up at phase + beta (beta = 128).  The helper centres every step on that: it
+    returns the staircase rotated by beta - Delta/2 places, so the look-up rounds at half a step, phase in
+    [Delta s - Delta/2, Delta s + Delta/2) reads step s, for every Delta.  On clear values (ct_matmul_eval_plain)
+    read the tables the same way, at Delta s + beta.  An output sums 2 inner bootstrap outputs: choose p with
+    Delta/2 above their summed noise."""
+    beta = 128
+    if q < 8 or q & (q - 1):
+        raise ValueError(f"product_tables: q must be a power of two >= 8, got {q}")
+    if p < 4 or p & (p - 1) or 2 * p > q:
+        raise ValueError(f"product_tables: p must be a power of two with 4 <= p <= q/2 = {q // 2}, got {p}")
+    delta = q // p
+    if not negacyclic:
+        j = np.arange(q, dtype=np.int64) // delta
+        s = np.where(j < p // 2, j, j - p)
+        stairs = delta * ((s * s // 4) % p)
+    else:
+        h = np.arange(q // 2, dtype=np.int64) // delta
+        s = np.where(h < p // 4, h, h - p // 2)
+        sq = delta * ((s * s // 4) % p)
+        half = np.where(h < p // 4, sq, (q - sq) % q)
+        half[half == 0] = 1
+        stairs = np.concatenate([half, q - half])
+    lut = np.roll(stairs, beta - delta // 2).astype(np.uint64)
+    return np.stack([lut, lut])
 
 
 def host_selftest(p: Params):

@@ -9,7 +9,7 @@ from contextlib import contextmanager
 
 import numpy as np
 
-from .capi import (BINGATE, Conv2d, Info, Knobs, Params, Pool2d, TfheError, check, conv2d_shape, lib, max_table,
+from .capi import (BINGATE, Conv2d, CtMatMul, Info, Knobs, Params, Pool2d, TfheError, check, conv2d_shape, lib, max_table,
                    pool2d_shape)
 
 
@@ -566,6 +566,51 @@ class BinFHEContextHIP:
                                                     q or self.params.q, C.c_void_p(d_lut), C.c_void_p(d_out),
                                                     C.c_void_p(stream)),
                     "tfhe_eval_pool2d_device")
+
+    # -- products of two encrypted tensors: sum_k EvalFunc(x + y, luts[0]) - EvalFunc(x - y, luts[1]) --
+    def EvalCtMatMul(self, x, y, luts, transposed=False, q=None):
+        """x[instances, R, K, n+1] mod q times y[instances, K, C, n+1], or y[K, C, n+1] shared by every instance
+        (encrypted weights); with transposed the K and C axes of y are swapped (Q K^T) -> [instances, R, C, n+1]:
+        out[i, r, c] = sum_k EvalFunc(x[i, r, k] + y[i, k, c], luts[0]) - EvalFunc(x[i, r, k] - y[i, k, c], luts[1])
+        mod q, luts[2, q].  With tfhe_amd.product_tables(q, p) it is the matrix product of the messages mod p.  Host
+        arrays staged through the first device (tfhe_eval_ct_matmul)."""
+        w, qq = self.params.n + 1, q or self.params.q
+        x, y = _u64(x), _u64(y)
+        if x.ndim != 4 or 0 in x.shape or x.shape[3] != w:
+            raise ValueError(f"EvalCtMatMul: x: expected shape (instances, R, K, {w}), got {x.shape}")
+        n, K = x.shape[0], x.shape[2]
+        kc = f"C, {K}" if transposed else f"{K}, C"
+        if y.ndim not in (3, 4) or 0 in y.shape or y.shape[-1] != w or y.shape[-2 if transposed else -3] != K or \
+                (y.ndim == 4 and y.shape[0] != n):
+            raise ValueError(f"EvalCtMatMul: y: expected shape ({n}, {kc}, {w}) or ({kc}, {w}), got {y.shape}")
+        desc = CtMatMul(x.shape[1], K, y.shape[-3 if transposed else -2], transposed, y.ndim == 3)
+        luts = _u64(luts)
+        if luts.shape != (2, qq):
+            raise ValueError(f"EvalCtMatMul: tables must have shape (2, {qq}), got {luts.shape}")
+        out = np.empty((n, desc.rows, desc.cols, w), dtype=np.uint64)
+        self._check(self._L.tfhe_eval_ct_matmul(self._h, C.byref(desc), n, x.ravel(), y.ravel(), qq, luts.ravel(),
+                                                out.ravel()), "tfhe_eval_ct_matmul")
+        return out
+
+    def EvalCtMul(self, x, y, luts, q=None):
+        """Elementwise on equal shapes [..., n+1]: out = EvalFunc(x + y, luts[0]) - EvalFunc(x - y, luts[1]) mod q;
+        with tfhe_amd.product_tables(q, p) the product of the messages mod p.  EvalCtMatMul with R = K = C = 1 and
+        one instance per element."""
+        w = self.params.n + 1
+        x, y = _u64(x), _u64(y)
+        if x.ndim < 1 or x.shape[-1] != w or x.size == 0 or x.shape != y.shape:
+            raise ValueError(f"EvalCtMul: expected two equal shapes (..., {w}), got {x.shape} and {y.shape}")
+        out = self.EvalCtMatMul(x.reshape(-1, 1, 1, w), y.reshape(-1, 1, 1, w), luts, q=q)
+        return out.reshape(x.shape)
+
+    def EvalCtMatMulDevice(self, desc, instances, d_x, d_y, d_luts, d_out, q=None, stream=0):
+        """desc: tfhe_amd.CtMatMul; d_x[instances][rows][inner][n+1], d_y[instances][inner][cols][n+1] (its axes as
+        desc.y_transposed / desc.y_shared say), d_luts[2][q] -> d_out[instances][rows][cols][n+1], device pointers; no
+        input word is written."""
+        self._check(self._L.tfhe_eval_ct_matmul_device(self._h, C.byref(desc), instances, C.c_void_p(d_x),
+                                                       C.c_void_p(d_y), q or self.params.q, C.c_void_p(d_luts),
+                                                       C.c_void_p(d_out), C.c_void_p(stream)),
+                    "tfhe_eval_ct_matmul_device")
 
     # -- device-resident (pointers are integers, e.g. torch tensor.data_ptr()) --
     def EvalBinGateDevice(self, gate, B, d_ct1, d_ct2, d_out, q=None, stream=0):
