@@ -146,6 +146,15 @@ def openfhe_ntt(Q: int, N: int, polys, inverse: bool = False) -> np.ndarray:
     return out
 
 
+def signed_digit_decompose(p: Params, acc) -> np.ndarray:
+    """SignedDigitDecompose of acc[B][2][N] -> [B][dG2][N]: row j + 2 l = kept digit l of polynomial j mod Q."""
+    acc = np.ascontiguousarray(acc, dtype=np.uint64).reshape(-1, 2, p.N)
+    out = np.empty((acc.shape[0], p.dG2, p.N), dtype=np.uint64)
+    for x, y in zip(acc, out):
+        lib().or_signed_digit_decompose(C.byref(p), x.ravel(), y.ravel())
+    return out
+
+
 def splitmix(rng: Rng, count: int, mod: int) -> np.ndarray:
     out = np.empty(count, dtype=np.uint64)
     lib().or_splitmix_fill(C.byref(rng), count, mod, out)

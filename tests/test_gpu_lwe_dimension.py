@@ -99,7 +99,7 @@ SECONDS = {}  # family -> seconds in its items
 class Ctx:
     """One context of a case at one n with its oracle, the inputs of (a) and the oracle's memoised answers."""
 
-    def __init__(self, oracle, case, n, keys, tag):
+    def __init__(self, oracle, case, n, keys, tag, calls=None):
         from test_gpu_modulus_edges import _edge_pair, _late_wrap_inputs
 
         self.case, self.n, self.spec = case, n, CASES[case]
@@ -115,13 +115,16 @@ class Ctx:
         k = self.ctx.info().br_kernel
         print(f"{case} n = {n}{tag}: N = {self.cp.N}, Q = {self.cp.Q}, br_kernel = {k}")
         assert k == self.spec["kernel"], (case, n, k)
+        self._want = {}
+        if calls is not None:  # calls(op) -> [(what, a, amod, acc)]: another module's inputs
+            self.calls = calls(self.op)
+            return
         a, self.acc = ld.sweep_inputs(self.op, 7 + n)
         self.calls = [(f"a mod {m}", a[m], m, self.acc) for m in sorted(a)]
         if self.spec.get("late_wrap") and n >= 2:  # a_i = 0 for i < n - 1: the vote flag of parity (n - 1) & 1
             la, lacc = _late_wrap_inputs(self.op, 11 + n, ld.B)
             assert not la[:, :-1].any() and la[:, -1].all()
             self.calls.append(("late wrap", la, int(self.op.q), lacc))
-        self._want = {}
 
     def _keep(self, keys):
         def wrapped(cp, op):
@@ -147,12 +150,12 @@ class Pool:
     def __init__(self, oracle, name):
         self.oracle, self.name, self.made = oracle, name, {}
 
-    def get(self, case, n, keys=None, tag=""):
+    def get(self, case, n, keys=None, tag="", calls=None):
         assert CASES[case]["family"] == self.name
         key = (case, n, tag)
         if key not in self.made:
             seed = 1000 * (list(CASES).index(case) + 1) + n
-            self.made[key] = Ctx(self.oracle, case, n, keys or ld.kat_edge_keys(self.oracle, seed), tag)
+            self.made[key] = Ctx(self.oracle, case, n, keys or ld.kat_edge_keys(self.oracle, seed), tag, calls)
         return self.made[key]
 
     def close(self):
