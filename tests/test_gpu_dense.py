@@ -148,6 +148,31 @@ def test_shape_and_argument_errors(env):
     assert e.value.status == 1
 
 
+def test_host_block_sum_overflow_is_refused(env):
+    """Sizes whose every product passes the matrix-product checks but whose sum, the one block
+    ct | matrix | bias | lut | out of the host-array form, leaves size_t in bytes: refused as an argument error
+    before anything is allocated or copied (the arrays passed are far smaller than the sizes claim), and the
+    bootstraps counter does not move."""
+    op, ctx, _ = env
+    q, w = op.q, op.n + 1
+    lim = (2**64 - 1) // 8  # words whose bytes fit size_t
+    K = cols = 2**30
+    instances = lim // w // K  # the most the per-product checks admit
+    wi, wm, wl, wo = instances * K * w, K * cols, q, instances * cols * w
+    assert instances >= 1 and max(wi, wm, wo, K * w, cols * w) <= lim  # each product fits ...
+    assert wi + wm + cols + wl + wo > lim  # ... their sum does not
+    ct = np.zeros((1, 1, w), dtype=np.uint64)
+    mat = np.zeros((1, 1), dtype=np.int64)
+    out = np.zeros((1, 1, w), dtype=np.uint64)
+    lut = _luts(q)["negacyclic"]
+    L = ctx._L
+    before = ctx.info().bootstraps
+    assert L.tfhe_eval_dense(ctx._h, instances, K, ct.ravel(), cols, mat.ravel(), None, q, lut, out.ravel()) == 1
+    assert b"EvalDense: sizes overflow" in L.tfhe_last_error()
+    assert ctx.info().bootstraps == before
+    assert not out.any()
+
+
 def test_slices_beyond_the_chunk(shared_kat):
     """70,001 results on STD128 (K = 2, one instance): EvalFunc runs in two slices, cut at 65,536 like a circuit
     level (the scratch never exceeds max_chunk, so no smaller batch crosses a slice).  Compared with EvalFuncDevice

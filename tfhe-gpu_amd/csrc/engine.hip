@@ -196,6 +196,12 @@ struct DevBuf {
     }
 };
 
+// drains a stream when its scope ends, so that the DevBufs declared before it free memory no kernel still uses
+struct Drain {
+    hipStream_t s;
+    ~Drain() { hipStreamSynchronize(s); }
+};
+
 constexpr size_t kStageBytes = (size_t)8 << 20;
 
 }  // namespace
@@ -758,21 +764,24 @@ tfhe_status dev_func(tfhe_ctx* c, Device& d, int prop, const uint64_t* ct, uint6
 // EvalFunc with one table per channel: ciphertext i of a flat batch uses table (i / inner) mod T
 // ---------------------------------------------------------------------------
 // The tables of one call, classified one by one on the host.  meta[t] = {class, class-0 / 1 / 2 tables below t}.
+// T = 0: one table [q] shared by every ciphertext, classified like a first table (its class is cls[0], so
+// classes = 1); no index rule applies and dev_func_tables runs plain dev_func.
 struct TabCall {
-    const uint64_t* d_luts = nullptr;  // device [T][q]
+    const uint64_t* d_luts = nullptr;  // device [max(T, 1)][q]
     size_t T = 0;
-    std::vector<uint8_t> cls;    // [T]
-    std::vector<uint32_t> meta;  // [T][4]
+    std::vector<uint8_t> cls;    // [max(T, 1)]
+    std::vector<uint32_t> meta;  // [max(T, 1)][4]
     uint64_t ntab[3] = {};
     int classes = 0;             // how many of the three are present
     const uint4* d_meta = nullptr;  // Device::tab_meta, uploaded by tab_upload when classes > 1
 };
 
 void tab_classify(TabCall& tc, const uint64_t* luts, size_t T, uint64_t q) {
+    const size_t count = std::max<size_t>(T, 1);
     tc.T = T;
-    tc.cls.resize(T);
-    tc.meta.resize(4 * T);
-    for (size_t t = 0; t < T; ++t) {
+    tc.cls.resize(count);
+    tc.meta.resize(4 * count);
+    for (size_t t = 0; t < count; ++t) {
         const int k = check_input_function(luts + t * q, q, q);
         tc.cls[t] = (uint8_t)k;
         tc.meta[4 * t] = (uint32_t)k;
@@ -792,7 +801,7 @@ void tab_count(const TabCall& tc, uint64_t inner, uint64_t i, uint64_t n[3]) {
 // the class table on the device, inside the frame (the buffer is the scratch's: earlier users are done once the
 // stream reaches the copy); the host waits, so tc may go out of scope and a later call may overwrite tc.meta
 tfhe_status tab_upload(Device& d, TabCall& tc) {
-    if (tc.classes < 2) return TFHE_OK;
+    if (tc.classes < 2) return TFHE_OK;  // always so for a shared table (T = 0: one table, one class), so T >= 2 below
     HCHECK(hipMemcpyAsync(d.tab_meta, tc.meta.data(), tc.T * 16, hipMemcpyHostToDevice, d.stream));
     HCHECK(hipStreamSynchronize(d.stream));
     tc.d_meta = reinterpret_cast<const uint4*>(d.tab_meta);
@@ -803,8 +812,10 @@ tfhe_status tab_upload(Device& d, TabCall& tc) {
 // runs dev_func on the caller's rows with the table chosen by the index rule: no row is copied.  Otherwise the
 // rows are gathered by class into lwe[3] (their tables into lwe[5]), each class present runs dev_func on its run
 // of rows into lwe[4], and the results are scattered: 2 + at most 3 pipelines, whatever T and inner are.
+// A shared table (T = 0) is plain dev_func: no index rule, no TabSel.
 tfhe_status dev_func_tables(tfhe_ctx* c, Device& d, const TabCall& tc, uint64_t inner, uint64_t first,
                             const uint64_t* ct, uint64_t q, uint64_t* out, size_t B) {
+    if (tc.T == 0) return dev_func(c, d, tc.cls[0], ct, q, tc.d_luts, 0, out, B);
     uint64_t lo[3], hi[3];
     tab_count(tc, inner, first, lo);
     tab_count(tc, inner, first + B, hi);
@@ -916,18 +927,11 @@ tfhe_status dev_mul_matrix(tfhe_ctx* c, Device& d, size_t instances, size_t K, c
 }
 
 // z = W^T x + bias mod q into d.dense_z, then EvalFunc over the flat batch of instances cols ciphertexts in
-// slices of the scratch, as dev_circuit slices a level.  tc: one table per column (inner = 1) instead of d_lut
-tfhe_status dev_dense(tfhe_ctx* c, Device& d, int prop, size_t instances, size_t K, const uint64_t* ct, size_t cols,
-                      const int64_t* matrix, const uint64_t* bias, uint64_t q, const uint64_t* d_lut, uint64_t* out,
-                      const TabCall* tc = nullptr) {
+// slices of the scratch, as dev_circuit slices a level.  tc: one shared table, or one per column (inner = 1)
+tfhe_status dev_dense(tfhe_ctx* c, Device& d, size_t instances, size_t K, const uint64_t* ct, size_t cols,
+                      const int64_t* matrix, const uint64_t* bias, uint64_t q, const TabCall& tc, uint64_t* out) {
     SCHECK(dev_mul_matrix(c, d, instances, K, ct, cols, matrix, bias, q, d.dense_z));
-    if (tc) return dev_func_tables_batch(c, d, *tc, 1, d.dense_z, q, out, instances * cols);
-    const size_t w = c->p.n + 1, total = instances * cols, slice = std::min(d.sc.cap, c->max_chunk);
-    for (size_t first = 0; first < total; first += slice) {
-        const size_t B = std::min(slice, total - first);
-        SCHECK(dev_func(c, d, prop, d.dense_z + first * w, q, d_lut, 0, out + first * w, B));
-    }
-    return TFHE_OK;
+    return dev_func_tables_batch(c, d, tc, 1, d.dense_z, q, out, instances * cols);
 }
 
 // ---------------------------------------------------------------------------
@@ -942,20 +946,11 @@ tfhe_status dev_conv2d(tfhe_ctx* c, Device& d, const ConvGeom& g, size_t instanc
 }
 
 // z = conv(x) + bias mod q into d.dense_z, then EvalFunc over the flat batch of instances c_out oh ow ciphertexts
-// in slices, as dev_dense.  tc: one table per output plane (inner = oh ow) instead of d_lut
-tfhe_status dev_conv_layer(tfhe_ctx* c, Device& d, int prop, const ConvGeom& g, size_t instances, const uint64_t* ct,
-                           const int64_t* weight, const uint64_t* bias, uint64_t q, const uint64_t* d_lut,
-                           uint64_t* out, const TabCall* tc = nullptr) {
+// in slices, as dev_dense.  tc: one shared table, or one per output plane (inner = oh ow)
+tfhe_status dev_conv_layer(tfhe_ctx* c, Device& d, const ConvGeom& g, size_t instances, const uint64_t* ct,
+                           const int64_t* weight, const uint64_t* bias, uint64_t q, const TabCall& tc, uint64_t* out) {
     SCHECK(dev_conv2d(c, d, g, instances, ct, weight, bias, q, d.dense_z));
-    if (tc)
-        return dev_func_tables_batch(c, d, *tc, (uint64_t)g.oh * g.ow, d.dense_z, q, out,
-                                     instances * g.c_out * g.oh * g.ow);
-    const size_t w = c->p.n + 1, total = instances * g.c_out * g.oh * g.ow, slice = std::min(d.sc.cap, c->max_chunk);
-    for (size_t first = 0; first < total; first += slice) {
-        const size_t B = std::min(slice, total - first);
-        SCHECK(dev_func(c, d, prop, d.dense_z + first * w, q, d_lut, 0, out + first * w, B));
-    }
-    return TFHE_OK;
+    return dev_func_tables_batch(c, d, tc, (uint64_t)g.oh * g.ow, d.dense_z, q, out, instances * g.c_out * g.oh * g.ow);
 }
 
 // ---------------------------------------------------------------------------
@@ -964,11 +959,10 @@ tfhe_status dev_conv_layer(tfhe_ctx* c, Device& d, int prop, const ConvGeom& g, 
 // Round by round: the round's pairs over every instance and plane are one flat batch, item = plane nrec + record;
 // per slice of the scratch, z = a - b into the first half of d.dense_z, EvalFunc into the second, dst = f + b into
 // d.pool_slots or out.  A round reads inputs and earlier rounds' slots and writes fresh slots and outputs, so
-// its slices are independent.  Positions with one valid tap are copied.  tc: one table per plane instead of d_lut
+// its slices are independent.  Positions with one valid tap are copied.  tc: one shared table, or one per plane
 // (item = plane nrec + record, so inner is the round's nrec and the table is plane mod c).
-tfhe_status dev_pool2d(tfhe_ctx* c, Device& d, int prop, const Device::PoolPlanDev& pp, size_t instances,
-                       const uint64_t* ct, uint64_t q, const uint64_t* d_lut, uint64_t* out,
-                       const TabCall* tc = nullptr) {
+tfhe_status dev_pool2d(tfhe_ctx* c, Device& d, const Device::PoolPlanDev& pp, size_t instances, const uint64_t* ct,
+                       uint64_t q, const TabCall& tc, uint64_t* out) {
     const PoolGeom& g = pp.g;
     const size_t w = c->p.n + 1, planes = instances * g.c, slice = std::min(d.sc.cap, c->max_chunk);
     PoolArgs a{};
@@ -984,8 +978,7 @@ tfhe_status dev_pool2d(tfhe_ctx* c, Device& d, int prop, const Device::PoolPlanD
         for (a.first = 0; a.first < total; a.first += slice) {
             a.count = std::min(slice, total - a.first);
             HCHECK(launch_pool_diff(a, z, d.stream));
-            if (tc) SCHECK(dev_func_tables(c, d, *tc, a.nrec, a.first, z, q, f, a.count));
-            else SCHECK(dev_func(c, d, prop, z, q, d_lut, 0, f, a.count));
+            SCHECK(dev_func_tables(c, d, tc, a.nrec, a.first, z, q, f, a.count));
             HCHECK(launch_pool_add(a, f, d.stream));
         }
     }
@@ -2557,56 +2550,107 @@ tfhe_status run_device_op(tfhe_ctx* c, size_t B, const void* d_out, void* stream
     d.stream = saved;
     return st != TFHE_OK ? st : rel;
 }
+
+// One input of a host-array call: `words` words at `host`, in rows of `row` words.  A null host (an absent bias)
+// keeps its room in the block, is not copied, and reaches the device call as null.
+struct HostSeg {
+    const void* host;
+    size_t row, words;
+};
+
+// Frame of the host-array form of a device-resident op, on the context's first device: one block
+// "in[0] | in[1] | ... | out" whose size in bytes must fit size_t (the callers check their products, this checks
+// the sum), the inputs staged in, on_device(device segments, d_out), the output (rows of n+1 words) staged back,
+// and the stream drained before the block is freed, on every path.
+template <typename F>
+tfhe_status run_from_host(tfhe_ctx* c, const char* op, std::initializer_list<HostSeg> in, uint64_t* out,
+                          size_t out_words, F&& on_device) {
+    const size_t lim = SIZE_MAX / sizeof(uint64_t);
+    size_t total = out_words;
+    bool fits = total <= lim;
+    for (const HostSeg& seg : in) {
+        fits = fits && seg.words <= lim - total;
+        if (fits) total += seg.words;
+    }
+    if (!fits) return fail(TFHE_ERR_INVALID_ARGUMENT, std::string(op) + ": sizes overflow");
+    Device& d = c->devs[0];
+    HCHECK(hipSetDevice(d.id));
+    DevBuf buf;
+    HCHECK(hipMalloc(&buf.p, total * sizeof(uint64_t)));
+    uint64_t* at = buf.as<uint64_t>();
+    std::vector<const uint64_t*> d_in;
+    tfhe_status st = TFHE_OK;
+    for (const HostSeg& seg : in) {
+        d_in.push_back(seg.host ? at : nullptr);
+        if (st == TFHE_OK && seg.host)
+            st = h2d_staged(d, at, flat_rows(static_cast<const uint64_t*>(seg.host), seg.row), seg.words, d.stream);
+        at += seg.words;
+    }
+    if (st == TFHE_OK) st = on_device(d_in.data(), at);
+    if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, c->p.n + 1), at, out_words, d.stream);
+    const hipError_t e = hipStreamSynchronize(d.stream);  // before the block is freed, on every path
+    if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string(op) + ": " + hipGetErrorString(e));
+    return st;
+}
 }  // namespace
 }  // extern "C++"
 
 extern "C++" {
 namespace {
-// What every call with one table per channel checks of (q, num_luts, inner) before any device call (N = 0: no
-// context, q need only be a power of two >= 8); every message names the field.
+// The table size every EvalFunc layer admits (N = 0: no context, only the power of two is checked).
+tfhe_status check_table_q(const char* who, uint64_t q, uint64_t N) {
+    if (q >= 8 && (q & (q - 1)) == 0 && (N == 0 || (2ull * N) % q == 0)) return TFHE_OK;
+    return fail(TFHE_ERR_INVALID_ARGUMENT,
+                std::string(who) + ": q must be a power of two >= 8" + (N ? " that divides 2N" : ""));
+}
+
+// What every call with one table per channel checks of (q, num_luts, inner) before any device call; every
+// message names the field.
 tfhe_status check_tables_args(const char* who, uint64_t q, uint64_t N, size_t num_luts, size_t inner) {
     const auto bad = [who](const std::string& what) {
         return fail(TFHE_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what);
     };
     if (num_luts == 0) return bad("num_luts is 0");
     if (inner == 0) return bad("inner is 0");
-    if (q < 8 || (q & (q - 1)) != 0 || (N && (2ull * N) % q != 0))
-        return bad(N ? "q must be a power of two >= 8 that divides 2N" : "q must be a power of two >= 8");
+    SCHECK(check_table_q(who, q, N));
     if (num_luts > UINT32_MAX || num_luts > SIZE_MAX / sizeof(uint64_t) / q) return bad("num_luts q overflows");
     if (inner > SIZE_MAX / num_luts) return bad("inner num_luts overflows");
     return TFHE_OK;
 }
 
-// The host tables of a host-array call: an arbitrary one at q > N is refused before anything is allocated or
-// launched.  num_luts = 0: one shared table; else lut[num_luts][q], classified once into `pre` for tab_prepare.
+// The host tables of a host-array call (num_luts = 0: one shared table; else lut[num_luts][q]), classified once
+// into `pre` for tab_prepare: an arbitrary one at q > N is refused before anything is allocated or launched.
 tfhe_status check_host_tables(tfhe_ctx* c, const uint64_t* lut, size_t num_luts, uint64_t q, TabCall& pre) {
-    bool arbitrary;
-    if (num_luts) {
-        tab_classify(pre, lut, num_luts, q);
-        arbitrary = pre.ntab[2] != 0;
-    } else {
-        arbitrary = check_input_function(lut, q, q) == 2;
-    }
-    if (arbitrary && q > c->p.N) return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
+    tab_classify(pre, lut, num_luts, q);
+    if (pre.ntab[2] && q > c->p.N) return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
     return TFHE_OK;
 }
 
-// The tables of a device call, before its frame opens: the T q words read back once and classified one by one,
-// the call refused when an arbitrary table meets q > N, and the class table's store in place.  pre: the classes
-// of the same tables, known already (the host-array forms classify their host copy: no read-back, no second pass).
+// `words` words of a device table on the host, once the stream's earlier work is done
+tfhe_status tab_read_back(Device& d, void* stream, const uint64_t* d_luts, size_t words, std::vector<uint64_t>& host) {
+    host.resize(words);
+    hipStream_t s = stream ? (hipStream_t)stream : d.stream;
+    HCHECK(hipMemcpyAsync(host.data(), d_luts, words * 8, hipMemcpyDeviceToHost, s));
+    HCHECK(hipStreamSynchronize(s));
+    return TFHE_OK;
+}
+
+// The tables of a device call, before its frame opens: the T q words (T = 0: the q words of the shared table)
+// read back once and classified one by one, the call refused when an arbitrary table meets q > N, and the class
+// table's store in place.  pre: the classes of the same tables, known already (the host-array forms classify
+// their host copy: no read-back, no second pass).
 tfhe_status tab_prepare(tfhe_ctx* c, Device& d, void* stream, uint64_t q, const uint64_t* d_luts, size_t T, TabCall& tc,
                         const TabCall* pre = nullptr) {
     if (pre) {
         tc = *pre;
     } else {
-        std::vector<uint64_t> host(T * q);
-        hipStream_t s = stream ? (hipStream_t)stream : d.stream;
-        HCHECK(hipMemcpyAsync(host.data(), d_luts, T * q * 8, hipMemcpyDeviceToHost, s));
-        HCHECK(hipStreamSynchronize(s));
+        std::vector<uint64_t> host;
+        SCHECK(tab_read_back(d, stream, d_luts, std::max<size_t>(T, 1) * q, host));
         tab_classify(tc, host.data(), T, q);
     }
     tc.d_luts = d_luts;
     if (tc.ntab[2] && q > c->p.N) return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
+    // more than one class needs T >= 2: a shared table (T = 0) never reaches the class table's store
     if (tc.classes > 1) SCHECK(ensure_words(d, d.tab_meta, d.tab_meta_words, 2 * T));
     return TFHE_OK;
 }
@@ -2673,21 +2717,11 @@ tfhe_status tfhe_eval_func_tables(tfhe_ctx* c, size_t B, const uint64_t* ct, uin
         SCHECK(check_func_tables_call(c, B, ct, q, luts, num_luts, inner, out));
         TabCall pre;
         SCHECK(check_host_tables(c, luts, num_luts, q, pre));
-        Device& d = c->devs[0];
-        HCHECK(hipSetDevice(d.id));
-        const size_t w = c->p.n + 1, wc = B * w, wl = num_luts * q;
-        if (wc > (SIZE_MAX / sizeof(uint64_t) - wl) / 2) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalFuncTables: sizes overflow");
-        // one block: ct | luts | out
-        DevBuf buf;
-        HCHECK(hipMalloc(&buf.p, (wc + wl + wc) * sizeof(uint64_t)));
-        uint64_t *dct = buf.as<uint64_t>(), *dl = dct + wc, *dout = dl + wl;
-        tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wc, d.stream);
-        if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(luts, q), wl, d.stream);
-        if (st == TFHE_OK) st = func_tables_on_device(c, B, dct, q, dl, num_luts, inner, dout, nullptr, &pre);
-        if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wc, d.stream);
-        const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
-        if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalFuncTables: ") + hipGetErrorString(e));
-        return st;
+        const size_t w = c->p.n + 1;
+        return run_from_host(c, "EvalFuncTables", {{ct, w, B * w}, {luts, q, num_luts * q}}, out, B * w,
+                             [&](const uint64_t* const* in, uint64_t* d_out) {
+                                 return func_tables_on_device(c, B, in[0], q, in[1], num_luts, inner, d_out, nullptr, &pre);
+                             });
     });
 }
 
@@ -2711,16 +2745,11 @@ tfhe_status tfhe_eval_func_device(tfhe_ctx* c, size_t B, const uint64_t* d_ct, u
         if (!d_ct || !d_lut || !d_out) return fail(TFHE_ERR_INVALID_ARGUMENT, "null argument");
         if (q < 4 || (2ull * c->p.N) % q) return fail(TFHE_ERR_INVALID_ARGUMENT, "q must divide 2N");
         // the first LUT classifies the batch (binfhe-base-scheme.cpp:697-698): q words to the host
-        std::vector<uint64_t> lut0(q);
-        hipStream_t s = stream ? (hipStream_t)stream : nullptr;
-        {
-            Device* dp = nullptr;
-            SCHECK(device_for(c, d_out, dp));
-            HCHECK(hipSetDevice(dp->id));
-            if (!s) s = dp->stream;
-            HCHECK(hipMemcpyAsync(lut0.data(), d_lut, q * 8, hipMemcpyDeviceToHost, s));
-            HCHECK(hipStreamSynchronize(s));
-        }
+        Device* dp = nullptr;
+        SCHECK(device_for(c, d_out, dp));
+        HCHECK(hipSetDevice(dp->id));
+        std::vector<uint64_t> lut0;
+        SCHECK(tab_read_back(*dp, stream, d_lut, q, lut0));
         const int prop = check_input_function(lut0.data(), q, q);
         return run_device_op(c, B, d_out, stream, [&](Device& d) {
             return dev_func(c, d, prop, d_ct, q, d_lut, per_ct_lut ? q : 0, d_out, B);
@@ -2782,18 +2811,11 @@ tfhe_status check_fcircuit_call(tfhe_ctx* c, const tfhe_fcircuit* circ, size_t i
 template <typename F>
 tfhe_status circuit_from_host(tfhe_ctx* c, uint32_t num_inputs, uint32_t num_outputs, size_t instances, const uint64_t* in,
                               uint64_t* out, F&& on_device) {
-    Device& d = c->devs[0];
-    HCHECK(hipSetDevice(d.id));
     const size_t w = c->p.n + 1, wi = (size_t)num_inputs * instances * w, wo = (size_t)num_outputs * instances * w;
-    DevBuf din, dout;
-    if (wi) HCHECK(hipMalloc(&din.p, wi * sizeof(uint64_t)));
-    HCHECK(hipMalloc(&dout.p, wo * sizeof(uint64_t)));
-    if (wi) SCHECK(h2d_staged(d, din.as<uint64_t>(), flat_rows(in, w), wi, d.stream));
-    tfhe_status st = on_device(din.as<uint64_t>(), dout.as<uint64_t>());
-    if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout.as<uint64_t>(), wo, d.stream);
-    const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffers are freed, on every path
-    if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalCircuit: ") + hipGetErrorString(e));
-    return st;
+    // one block in | out (d_out lies wi words into it); a circuit without inputs stages nothing and hands
+    // on_device a null d_in
+    return run_from_host(c, "EvalCircuit", {{wi ? in : nullptr, w, wi}}, out, wo,
+                         [&](const uint64_t* const* d_in, uint64_t* d_out) { return on_device(d_in[0], d_out); });
 }
 
 // d_out selects the device; the wire store and the plan are in place before the frame opens
@@ -2961,11 +2983,7 @@ tfhe_status tfhe_eval_decomp(tfhe_ctx* c, size_t B, const uint64_t* ct, uint64_t
             uint64_t *tmp = tmp_b.as<uint64_t>(), *fl = fl_b.as<uint64_t>(), *dig = dig_b.as<uint64_t>();
             std::vector<uint64_t> host_digit(chunk * w);
             tfhe_status st = TFHE_OK;
-            // every exit below leaves the stream drained before the DevBufs free their memory
-            struct Drain {
-                hipStream_t s;
-                ~Drain() { hipStreamSynchronize(s); }
-            } drain{d.stream};
+            Drain drain{d.stream};  // every exit below leaves the stream drained before the DevBufs free their memory
             for (size_t off = lo; off < lo + cnt && st == TFHE_OK; off += chunk) {
                 const size_t b = std::min(chunk, lo + cnt - off);
                 HCHECK(hipMemcpyAsync(tmp, ct + off * w, b * w * 8, hipMemcpyHostToDevice, d.stream));
@@ -3023,39 +3041,24 @@ tfhe_status check_dense_call(tfhe_ctx* c, size_t instances, size_t K, const void
     SCHECK(check_ctx(c));
     if (!ct || !matrix || !lut || !out) return fail(TFHE_ERR_INVALID_ARGUMENT, "null argument");
     SCHECK(check_mm_sizes(c, instances, K, cols, q));
-    if (q < 8 || (q & (q - 1)) != 0 || (2ull * c->p.N) % q != 0)
-        return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalDense: q must be a power of two >= 8 that divides 2N");
-    return TFHE_OK;
+    return check_table_q("EvalDense", q, c->p.N);
 }
 
-// d_out selects the device; the table's class comes from its first q words, read back once.  num_luts > 0:
-// d_lut is [num_luts = cols][q], one table per column
+// d_out selects the device; the tables are read back once and classified (pre: the host-array form's classes of
+// its host copy).  num_luts = 0: d_lut is one shared table [q]; else [num_luts = cols][q], one per column
 tfhe_status dense_on_device(tfhe_ctx* c, size_t instances, size_t K, const uint64_t* d_ct, size_t cols,
                             const int64_t* d_matrix, const uint64_t* d_bias, uint64_t q, const uint64_t* d_lut,
                             uint64_t* d_out, void* stream, size_t num_luts = 0, const TabCall* pre = nullptr) {
     Device* dp = nullptr;
     SCHECK(device_for(c, d_out, dp));
     HCHECK(hipSetDevice(dp->id));
-    if (num_luts) {
-        TabCall tc;
-        SCHECK(tab_prepare(c, *dp, stream, q, d_lut, num_luts, tc, pre));
-        SCHECK(ensure_words(*dp, dp->mm_mat, dp->mm_mat_words, K * cols));
-        SCHECK(ensure_words(*dp, dp->dense_z, dp->dense_z_words, instances * cols * (c->p.n + 1)));
-        return run_device_op(c, std::min(instances * cols, c->max_chunk), d_out, stream, [&](Device& d) {
-            SCHECK(tab_upload(d, tc));
-            return dev_dense(c, d, 0, instances, K, d_ct, cols, d_matrix, d_bias, q, d_lut, d_out, &tc);
-        });
-    }
-    std::vector<uint64_t> lut0(q);
-    hipStream_t s = stream ? (hipStream_t)stream : dp->stream;
-    HCHECK(hipMemcpyAsync(lut0.data(), d_lut, q * 8, hipMemcpyDeviceToHost, s));
-    HCHECK(hipStreamSynchronize(s));
-    const int prop = check_input_function(lut0.data(), q, q);
-    if (prop == 2 && q > c->p.N) return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
+    TabCall tc;
+    SCHECK(tab_prepare(c, *dp, stream, q, d_lut, num_luts, tc, pre));
     SCHECK(ensure_words(*dp, dp->mm_mat, dp->mm_mat_words, K * cols));
     SCHECK(ensure_words(*dp, dp->dense_z, dp->dense_z_words, instances * cols * (c->p.n + 1)));
     return run_device_op(c, std::min(instances * cols, c->max_chunk), d_out, stream, [&](Device& d) {
-        return dev_dense(c, d, prop, instances, K, d_ct, cols, d_matrix, d_bias, q, d_lut, d_out);
+        SCHECK(tab_upload(d, tc));
+        return dev_dense(c, d, instances, K, d_ct, cols, d_matrix, d_bias, q, tc, d_out);
     });
 }
 }  // namespace
@@ -3076,10 +3079,7 @@ tfhe_status tfhe_ciphertext_mul_matrix(tfhe_ctx* c, size_t K, const uint64_t* ct
         HCHECK(hipMalloc(&dct.p, K * w * 8));
         HCHECK(hipMalloc(&dm.p, K * cols * 8));
         HCHECK(hipMalloc(&dout.p, cols * w * 8));
-        struct Drain {
-            hipStream_t s;
-            ~Drain() { hipStreamSynchronize(s); }
-        } drain{d.stream};
+        Drain drain{d.stream};
         HCHECK(hipMemcpyAsync(dct.p, ct, K * w * 8, hipMemcpyHostToDevice, d.stream));
         HCHECK(hipMemcpyAsync(dm.p, matrix, K * cols * 8, hipMemcpyHostToDevice, d.stream));
         SCHECK(ensure_words(d, d.mm_mat, d.mm_mat_words, K * cols));
@@ -3134,25 +3134,13 @@ tfhe_status dense_from_host(tfhe_ctx* c, size_t instances, size_t K, const uint6
                             uint64_t* out, size_t num_luts) {
     TabCall pre;
     SCHECK(check_host_tables(c, lut, num_luts, q, pre));
-    Device& d = c->devs[0];
-    HCHECK(hipSetDevice(d.id));
-    const size_t w = c->p.n + 1, wi = instances * K * w, wm = K * cols, wo = instances * cols * w,
-                 wl = std::max<size_t>(num_luts, 1) * q;
-    // one block: ct | matrix | bias | lut | out
-    DevBuf buf;
-    HCHECK(hipMalloc(&buf.p, (wi + wm + cols + wl + wo) * sizeof(uint64_t)));
-    uint64_t *dct = buf.as<uint64_t>(), *dm = dct + wi, *db = dm + wm, *dl = db + cols, *dout = dl + wl;
-    tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wi, d.stream);
-    if (st == TFHE_OK) st = h2d_staged(d, dm, flat_rows(reinterpret_cast<const uint64_t*>(matrix), cols), wm, d.stream);
-    if (st == TFHE_OK && bias) st = h2d_staged(d, db, flat_rows(bias, cols), cols, d.stream);
-    if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(lut, q), wl, d.stream);
-    if (st == TFHE_OK)
-        st = dense_on_device(c, instances, K, dct, cols, reinterpret_cast<const int64_t*>(dm), bias ? db : nullptr, q,
-                             dl, dout, nullptr, num_luts, num_luts ? &pre : nullptr);
-    if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
-    const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
-    if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalDense: ") + hipGetErrorString(e));
-    return st;
+    const size_t w = c->p.n + 1, wl = std::max<size_t>(num_luts, 1) * q;
+    return run_from_host(
+        c, "EvalDense", {{ct, w, instances * K * w}, {matrix, cols, K * cols}, {bias, cols, cols}, {lut, q, wl}}, out,
+        instances * cols * w, [&](const uint64_t* const* in, uint64_t* d_out) {
+            return dense_on_device(c, instances, K, in[0], cols, reinterpret_cast<const int64_t*>(in[1]), in[2], q,
+                                   in[3], d_out, nullptr, num_luts, &pre);
+        });
 }
 }  // namespace
 }  // extern "C++"
@@ -3260,41 +3248,25 @@ tfhe_status check_conv_layer_call(tfhe_ctx* c, const tfhe_conv2d* desc, size_t i
                                   size_t& K) {
     SCHECK(check_conv_call(c, desc, instances, ct, weight, q, out, g, K));
     if (!lut) return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalConv2d: null lut");
-    if (q < 8 || (q & (q - 1)) != 0 || (2ull * c->p.N) % q != 0)
-        return fail(TFHE_ERR_INVALID_ARGUMENT, "EvalConv2d: q must be a power of two >= 8 that divides 2N");
-    return TFHE_OK;
+    return check_table_q("EvalConv2d", q, c->p.N);
 }
 
-// d_out selects the device; the table's class comes from its first q words, read back once.  num_luts > 0:
-// d_lut is [num_luts = c_out][q], one table per output plane
+// d_out selects the device; the tables as in dense_on_device.  num_luts = 0: d_lut is one shared table [q]; else
+// [num_luts = c_out][q], one per output plane
 tfhe_status conv_layer_on_device(tfhe_ctx* c, const ConvGeom& g, size_t K, size_t instances, const uint64_t* d_ct,
                                  const int64_t* d_weight, const uint64_t* d_bias, uint64_t q, const uint64_t* d_lut,
                                  uint64_t* d_out, void* stream, size_t num_luts = 0, const TabCall* pre = nullptr) {
     Device* dp = nullptr;
     SCHECK(device_for(c, d_out, dp));
     HCHECK(hipSetDevice(dp->id));
-    if (num_luts) {
-        TabCall tc;
-        SCHECK(tab_prepare(c, *dp, stream, q, d_lut, num_luts, tc, pre));
-        const size_t total = instances * g.c_out * g.oh * g.ow;
-        SCHECK(ensure_words(*dp, dp->mm_mat, dp->mm_mat_words, K * g.c_out));
-        SCHECK(ensure_words(*dp, dp->dense_z, dp->dense_z_words, total * (c->p.n + 1)));
-        return run_device_op(c, std::min(total, c->max_chunk), d_out, stream, [&](Device& d) {
-            SCHECK(tab_upload(d, tc));
-            return dev_conv_layer(c, d, 0, g, instances, d_ct, d_weight, d_bias, q, d_lut, d_out, &tc);
-        });
-    }
-    std::vector<uint64_t> lut0(q);
-    hipStream_t s = stream ? (hipStream_t)stream : dp->stream;
-    HCHECK(hipMemcpyAsync(lut0.data(), d_lut, q * 8, hipMemcpyDeviceToHost, s));
-    HCHECK(hipStreamSynchronize(s));
-    const int prop = check_input_function(lut0.data(), q, q);
-    if (prop == 2 && q > c->p.N) return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
+    TabCall tc;
+    SCHECK(tab_prepare(c, *dp, stream, q, d_lut, num_luts, tc, pre));
     const size_t total = instances * g.c_out * g.oh * g.ow;
     SCHECK(ensure_words(*dp, dp->mm_mat, dp->mm_mat_words, K * g.c_out));
     SCHECK(ensure_words(*dp, dp->dense_z, dp->dense_z_words, total * (c->p.n + 1)));
     return run_device_op(c, std::min(total, c->max_chunk), d_out, stream, [&](Device& d) {
-        return dev_conv_layer(c, d, prop, g, instances, d_ct, d_weight, d_bias, q, d_lut, d_out);
+        SCHECK(tab_upload(d, tc));
+        return dev_conv_layer(c, d, g, instances, d_ct, d_weight, d_bias, q, tc, d_out);
     });
 }
 }  // namespace
@@ -3348,25 +3320,13 @@ tfhe_status conv_layer_from_host(tfhe_ctx* c, const ConvGeom& g, size_t K, size_
                                  uint64_t* out, size_t num_luts) {
     TabCall pre;
     SCHECK(check_host_tables(c, lut, num_luts, q, pre));
-    Device& d = c->devs[0];
-    HCHECK(hipSetDevice(d.id));
-    const size_t w = c->p.n + 1, wi = instances * g.c_in * g.h * g.w * w, wm = K * g.c_out, nb = g.c_out,
+    const size_t w = c->p.n + 1, wi = instances * g.c_in * g.h * g.w * w, nb = g.c_out,
                  wo = instances * g.c_out * g.oh * g.ow * w, wl = std::max<size_t>(num_luts, 1) * q;
-    // one block: ct | weight | bias | lut | out
-    DevBuf buf;
-    HCHECK(hipMalloc(&buf.p, (wi + wm + nb + wl + wo) * sizeof(uint64_t)));
-    uint64_t *dct = buf.as<uint64_t>(), *dm = dct + wi, *db = dm + wm, *dl = db + nb, *dout = dl + wl;
-    tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wi, d.stream);
-    if (st == TFHE_OK) st = h2d_staged(d, dm, flat_rows(reinterpret_cast<const uint64_t*>(weight), K), wm, d.stream);
-    if (st == TFHE_OK && bias) st = h2d_staged(d, db, flat_rows(bias, nb), nb, d.stream);
-    if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(lut, q), wl, d.stream);
-    if (st == TFHE_OK)
-        st = conv_layer_on_device(c, g, K, instances, dct, reinterpret_cast<const int64_t*>(dm), bias ? db : nullptr,
-                                  q, dl, dout, nullptr, num_luts, num_luts ? &pre : nullptr);
-    if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
-    const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
-    if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalConv2d: ") + hipGetErrorString(e));
-    return st;
+    return run_from_host(c, "EvalConv2d", {{ct, w, wi}, {weight, K, K * nb}, {bias, nb, nb}, {lut, q, wl}}, out, wo,
+                         [&](const uint64_t* const* in, uint64_t* d_out) {
+                             return conv_layer_on_device(c, g, K, instances, in[0], reinterpret_cast<const int64_t*>(in[1]),
+                                                         in[2], q, in[3], d_out, nullptr, num_luts, &pre);
+                         });
 }
 }  // namespace
 }  // extern "C++"
@@ -3427,8 +3387,7 @@ tfhe_status pool_geometry(const tfhe_pool2d* d, PoolGeom& g, uint32_t& rounds, s
     return TFHE_OK;
 }
 
-// what the pooling calls check before any device call (N = 0: no context, q need only be a power of two >= 8);
-// `words` is n+1, or 1 for clear values
+// what the pooling calls check before any device call (N = 0: no context); `words` is n+1, or 1 for clear values
 tfhe_status check_pool_args(const char* who, const tfhe_pool2d* desc, size_t instances, const void* in, uint64_t q,
                             uint64_t N, const void* lut, const void* out, size_t words, PoolGeom& g, size_t& pairs) {
     const auto bad = [who](const std::string& what) {
@@ -3441,8 +3400,7 @@ tfhe_status check_pool_args(const char* who, const tfhe_pool2d* desc, size_t ins
     if (instances == 0) return bad("instances is 0");
     uint32_t rounds = 0;
     SCHECK(pool_geometry(desc, g, rounds, pairs));
-    if (q < 8 || (q & (q - 1)) != 0 || (N && (2ull * N) % q != 0))
-        return bad(N ? "q must be a power of two >= 8 that divides 2N" : "q must be a power of two >= 8");
+    SCHECK(check_table_q(who, q, N));
     size_t src = sizeof(uint64_t), res = sizeof(uint64_t), mid = sizeof(PoolRec);
     // inputs, outputs, and what the pairs can need at most: a record each; a slot and two flat rows each
     const bool ok = conv_mul(src, instances) && conv_mul(src, g.c) && conv_mul(src, g.h) && conv_mul(src, g.w) &&
@@ -3481,40 +3439,24 @@ tfhe_status pool_plan_on_device(Device& d, const PoolGeom& g, const Device::Pool
     return TFHE_OK;
 }
 
-// d_out selects the device; the table's class comes from its first q words, read back once.  num_luts > 0:
-// d_lut is [num_luts = c][q], one table per plane
+// d_out selects the device; the tables as in dense_on_device.  num_luts = 0: d_lut is one shared table [q]; else
+// [num_luts = c][q], one per plane
 tfhe_status pool_on_device(tfhe_ctx* c, const PoolGeom& g, size_t instances, const uint64_t* d_ct, uint64_t q,
                            const uint64_t* d_lut, uint64_t* d_out, void* stream, size_t num_luts = 0,
                            const TabCall* pre = nullptr) {
     Device* dp = nullptr;
     SCHECK(device_for(c, d_out, dp));
     HCHECK(hipSetDevice(dp->id));
-    if (num_luts) {
-        TabCall tc;
-        SCHECK(tab_prepare(c, *dp, stream, q, d_lut, num_luts, tc, pre));
-        const Device::PoolPlanDev* pp = nullptr;
-        SCHECK(pool_plan_on_device(*dp, g, pp));
-        const size_t w = c->p.n + 1, planes = instances * g.c, B = std::min(planes * pp->widest, c->max_chunk);
-        SCHECK(ensure_words(*dp, dp->dense_z, dp->dense_z_words, 2 * B * w));
-        SCHECK(ensure_words(*dp, dp->pool_slots, dp->pool_slots_words, planes * pp->slots * w));
-        return run_device_op(c, B, d_out, stream, [&](Device& d) {
-            SCHECK(tab_upload(d, tc));
-            return dev_pool2d(c, d, 0, *pp, instances, d_ct, q, d_lut, d_out, &tc);
-        });
-    }
-    std::vector<uint64_t> lut0(q);
-    hipStream_t s = stream ? (hipStream_t)stream : dp->stream;
-    HCHECK(hipMemcpyAsync(lut0.data(), d_lut, q * 8, hipMemcpyDeviceToHost, s));
-    HCHECK(hipStreamSynchronize(s));
-    const int prop = check_input_function(lut0.data(), q, q);
-    if (prop == 2 && q > c->p.N) return fail(TFHE_ERR_UNSUPPORTED, "arbitrary function needs q <= N");
+    TabCall tc;
+    SCHECK(tab_prepare(c, *dp, stream, q, d_lut, num_luts, tc, pre));
     const Device::PoolPlanDev* pp = nullptr;
     SCHECK(pool_plan_on_device(*dp, g, pp));
     const size_t w = c->p.n + 1, planes = instances * g.c, B = std::min(planes * pp->widest, c->max_chunk);
     SCHECK(ensure_words(*dp, dp->dense_z, dp->dense_z_words, 2 * B * w));
     SCHECK(ensure_words(*dp, dp->pool_slots, dp->pool_slots_words, planes * pp->slots * w));
     return run_device_op(c, B, d_out, stream, [&](Device& d) {
-        return dev_pool2d(c, d, prop, *pp, instances, d_ct, q, d_lut, d_out);
+        SCHECK(tab_upload(d, tc));
+        return dev_pool2d(c, d, *pp, instances, d_ct, q, tc, d_out);
     });
 }
 }  // namespace
@@ -3563,21 +3505,12 @@ tfhe_status pool_from_host(tfhe_ctx* c, const PoolGeom& g, size_t instances, con
                            const uint64_t* lut, uint64_t* out, size_t num_luts) {
     TabCall pre;
     SCHECK(check_host_tables(c, lut, num_luts, q, pre));
-    Device& d = c->devs[0];
-    HCHECK(hipSetDevice(d.id));
     const size_t w = c->p.n + 1, wi = instances * g.c * g.h * g.w * w, wo = instances * g.c * g.oh * g.ow * w,
                  wl = std::max<size_t>(num_luts, 1) * q;
-    // one block: ct | lut | out
-    DevBuf buf;
-    HCHECK(hipMalloc(&buf.p, (wi + wl + wo) * sizeof(uint64_t)));
-    uint64_t *dct = buf.as<uint64_t>(), *dl = dct + wi, *dout = dl + wl;
-    tfhe_status st = h2d_staged(d, dct, flat_rows(ct, w), wi, d.stream);
-    if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(lut, q), wl, d.stream);
-    if (st == TFHE_OK) st = pool_on_device(c, g, instances, dct, q, dl, dout, nullptr, num_luts, num_luts ? &pre : nullptr);
-    if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
-    const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
-    if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalPool2d: ") + hipGetErrorString(e));
-    return st;
+    return run_from_host(c, "EvalPool2d", {{ct, w, wi}, {lut, q, wl}}, out, wo,
+                         [&](const uint64_t* const* in, uint64_t* d_out) {
+                             return pool_on_device(c, g, instances, in[0], q, in[1], d_out, nullptr, num_luts, &pre);
+                         });
 }
 }  // namespace
 }  // extern "C++"
@@ -3625,8 +3558,8 @@ struct CtmmSizes {
     size_t products, x_rows, y_rows, out_rows;
 };
 
-// what the product calls check before any device call (N = 0: no context, q need only be a power of two >= 8);
-// `words` is n+1, or 1 for clear values; every message names the field
+// what the product calls check before any device call (N = 0: no context); `words` is n+1, or 1 for clear values;
+// every message names the field
 tfhe_status check_ct_matmul_args(const char* who, const tfhe_ct_matmul* m, size_t instances, uint64_t q, uint64_t N,
                                  size_t words, CtmmSizes& sz) {
     const auto bad = [who](const std::string& what) {
@@ -3639,8 +3572,7 @@ tfhe_status check_ct_matmul_args(const char* who, const tfhe_ct_matmul* m, size_
     if (m->cols == 0) return bad("cols is 0");
     if (m->y_transposed > 1) return bad("y_transposed must be 0 or 1");
     if (m->y_shared > 1) return bad("y_shared must be 0 or 1");
-    if (q < 8 || (q & (q - 1)) != 0 || (N && (2ull * N) % q != 0))
-        return bad(N ? "q must be a power of two >= 8 that divides 2N" : "q must be a power of two >= 8");
+    SCHECK(check_table_q(who, q, N));
     // the inputs and the output in bytes, and what a slice can need at most: four flat rows per product
     size_t xs = 1, ys = 1, os = 1, mid = 4 * sizeof(uint64_t);
     const bool ok = conv_mul(xs, instances) && conv_mul(xs, m->rows) && conv_mul(xs, m->inner) &&
@@ -3756,21 +3688,11 @@ tfhe_status tfhe_eval_ct_matmul(tfhe_ctx* c, const tfhe_ct_matmul* m, size_t ins
         SCHECK(check_ct_matmul_call(c, m, instances, x, y, q, luts, out, sz));
         TabCall pre;
         SCHECK(check_host_tables(c, luts, 2, q, pre));
-        Device& d = c->devs[0];
-        HCHECK(hipSetDevice(d.id));
-        const size_t w = c->p.n + 1, wx = sz.x_rows * w, wy = sz.y_rows * w, wl = 2 * q, wo = sz.out_rows * w;
-        // one block: x | y | luts | out
-        DevBuf buf;
-        HCHECK(hipMalloc(&buf.p, (wx + wy + wl + wo) * sizeof(uint64_t)));
-        uint64_t *dx = buf.as<uint64_t>(), *dy = dx + wx, *dl = dy + wy, *dout = dl + wl;
-        tfhe_status st = h2d_staged(d, dx, flat_rows(x, w), wx, d.stream);
-        if (st == TFHE_OK) st = h2d_staged(d, dy, flat_rows(y, w), wy, d.stream);
-        if (st == TFHE_OK) st = h2d_staged(d, dl, flat_rows(luts, q), wl, d.stream);
-        if (st == TFHE_OK) st = ct_matmul_on_device(c, *m, instances, sz, dx, dy, q, dl, dout, nullptr, &pre);
-        if (st == TFHE_OK) st = d2h_staged(d, flat_rows(out, w), dout, wo, d.stream);
-        const hipError_t e = hipStreamSynchronize(d.stream);  // before the buffer is freed, on every path
-        if (st == TFHE_OK && e != hipSuccess) st = fail(TFHE_ERR_DEVICE, std::string("EvalCtMatMul: ") + hipGetErrorString(e));
-        return st;
+        const size_t w = c->p.n + 1;
+        return run_from_host(c, "EvalCtMatMul", {{x, w, sz.x_rows * w}, {y, w, sz.y_rows * w}, {luts, q, 2 * q}}, out,
+                             sz.out_rows * w, [&](const uint64_t* const* in, uint64_t* d_out) {
+                                 return ct_matmul_on_device(c, *m, instances, sz, in[0], in[1], q, in[2], d_out, nullptr, &pre);
+                             });
     });
 }
 
